@@ -15,8 +15,18 @@ N > 1 shards kv heads over ranks (tensor parallel, worker.rs:584-591) -- total w
 of the [B, h*d] activations over RCCL/xGMI (multi_gpu.rs:141-179).
 
 Prints ONE JSON line on rank 0.  `value` = algorithmic HBM GB/s of the whole job with inputs
-resident in HBM; `roofline` prices the dominant kernel against 8 TB/s; `cpu_baseline` is the
-oracle's C restatement (oracle/c/oracle.c, OpenMP) timed on this box's host cores.
+resident in HBM; `roofline` prices the dominant kernel against 8 TB/s.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the line.
+--full adds everything else the benchmark measures or checks: the HBM traffic counter passes
+(rocprofv3 child runs), the end-to-end extras (tools/bench_extra.py; the tensor-parallel step for
+N > 1), the first-contact all-reduce preflight (N > 1), and `cpu_baseline` -- the oracle's C
+restatement (oracle/c/oracle.c, OpenMP) timed on the host cores -- with the check of the timed
+output against it.  --no-traffic / --no-extra / --no-cpu-baseline drop single parts of --full.
+
+--dump-outputs DIR writes what the timed path computed in its last step (the run_mha output, as
+float32) to DIR/attn_out.npy (DIR/attn_out_rank<R>.npy per rank for N > 1).  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -64,6 +74,9 @@ def main():
                          "paged attention shards by kv head with NO exchange step; the tensor-parallel all-reduces belong to the layer "
                          "and are timed, with both engines, in extra.tp_step")
     ap.add_argument("--cpu-sample-seqs", type=int, default=64)
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: traffic counter passes, end-to-end extras, "
+                                                        "preflight (N > 1), CPU baseline and the check of the timed output against it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the timed path's output of its last step to DIR/attn_out.npy (float32)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -153,9 +166,9 @@ def main():
         # came up -- it has never run across real links from this tree, and the headline must not depend on it)
         comm_note = "RCCL communicator; direct path: see tp_step.xgmi_setup" if comm is not None else "direct kernels only (no RCCL communicator)"
         # ---- first contact: every engine sums a known pattern at 16 B / 1 MiB / 64 MiB BEFORE anything is timed (pass / fail + us per pair, on
-        # stderr as it goes and in the line); a hang becomes a failed pair, never a lost headline.  ATOMA_BENCH_PREFLIGHT=0 skips it.
+        # stderr as it goes and in the line); a hang becomes a failed pair, never a lost headline.  --full only; ATOMA_BENCH_PREFLIGHT=0 skips it there.
         preflight = None
-        if os.environ.get("ATOMA_BENCH_PREFLIGHT", "1") != "0":
+        if args.full and os.environ.get("ATOMA_BENCH_PREFLIGHT", "1") != "0":
             try:
                 preflight = tp.preflight(ah, dist, rank, world, comm=comm, xgmi=xgmi, log=lambda m: (sys.stderr.write(m + "\n"), sys.stderr.flush()),
                                          timeout_s=float(os.environ.get("ATOMA_BENCH_PREFLIGHT_TIMEOUT", "60")))
@@ -223,6 +236,8 @@ def main():
     launch_ms = [a.elapsed_ms(b_) for a, b_ in ev]
     kern_ms = float(np.mean(launch_ms))
     gpu_out = do.numpy(np.uint16, q.shape)                  # what the timed region wrote (checked below against the CPU leg's output)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, gpu_out, rank, world)
 
     ms_per_step = wall * 1e3 / args.steps
     total_bytes = algorithmic_bytes(B, S, h, hk, d, page)           # whole job (all ranks)
@@ -274,7 +289,7 @@ def main():
     # WRITE_SIZE in separate runs of this same command, corrected as the MI355X guide prescribes:
     # tools/summarize_profiles.py); null when no profile of the default workload is present.
     measured = None
-    if world == 1 and not args.no_traffic and not os.environ.get("ATOMA_BENCH_CHILD"):
+    if args.full and world == 1 and not args.no_traffic and not os.environ.get("ATOMA_BENCH_CHILD"):
         measured = measure_traffic(sys.argv[1:])
     if measured is not None:
         out["roofline"]["traffic"] = int(measured["bytes"])
@@ -295,7 +310,7 @@ def main():
     # N = 1: the 8B decode step of configs[2], the prefill kernel, the configs[4] swap.  N > 1: the tensor-parallel decode step
     # of configs[3] (70B-shaped shard per rank, 2 all-reduces of [64, 8192] per layer) with RCCL and with the direct xGMI kernels.
     prefill_smp, extra_smp = None, {}
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         for b_ in (dkc, dvc, dq, do):
             b_.free()
         sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -356,7 +371,7 @@ def main():
             out["tp_step"] = tp_summary(extra.get("tp_step") or tp_progress, extra.get("error"))
 
     failed = False
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # the CPU baseline is an N = 1 leg
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:   # the CPU baseline is an N = 1 leg
         out["cpu_baseline"], o_cpu = cpu_baseline(args, bt, lens, slab_k, slab_v, q, n_pages, page_elems, hk_l, h_l)
         # ---- the timed region's output against the CPU leg's (the oracle's C restatement, here as the checker): the sequences the
         # baseline computed anyway, BASELINE.json's tolerance (1e-3 + one unit in the last place of bf16)
@@ -395,6 +410,22 @@ def main():
         print(json.dumps(out), flush=True)
     if failed:
         sys.exit(3)                                          # a line whose numbers come from wrong results must not pass for a measurement
+
+
+DUMP_LIMIT_BYTES = 60 * 10 ** 6     # all dumped arrays together, headers aside: under 64 MB
+
+
+def dump_outputs(path, out_bits, rank, world):
+    """The timed path's output ([B, 1, h, d] bf16 bits) as float32 in PATH/attn_out.npy (PATH/attn_out_rank<R>.npy for N > 1: each
+    rank's head shard).  Above its share of DUMP_LIMIT_BYTES a fixed, seeded sample of the sequences (ascending order) stands in."""
+    from halfs import to_f32, BF16
+    os.makedirs(path, exist_ok=True)
+    o = to_f32(out_bits, BF16)
+    limit = DUMP_LIMIT_BYTES // world
+    if o.nbytes > limit:
+        keep = limit // (o.nbytes // o.shape[0])
+        o = o[np.sort(np.random.default_rng(1).choice(o.shape[0], keep, replace=False))]
+    np.save(os.path.join(path, "attn_out.npy" if world == 1 else "attn_out_rank%d.npy" % rank), o)
 
 
 def verify_prefill_sample(smp):
@@ -480,17 +511,17 @@ def measure_traffic(argv):
     import tempfile
     if not shutil.which("rocprofv3"):
         return None
-    keep = [a for a in argv if a not in ("--no-extra", "--no-cpu-baseline", "--no-traffic")]
+    keep = [a for a in argv if a not in ("--no-extra", "--no-cpu-baseline", "--no-traffic", "--full")]
     drop_next = False
     child_args = []
-    for a in keep:                       # strip --steps / --warmup (and their values): the child runs 3 + 1
+    for a in keep:                       # strip --steps / --warmup (the child runs 3 + 1) and --dump-outputs (and their values)
         if drop_next:
             drop_next = False
             continue
-        if a in ("--steps", "--warmup"):
+        if a in ("--steps", "--warmup", "--dump-outputs"):
             drop_next = True
             continue
-        if a.startswith("--steps=") or a.startswith("--warmup="):
+        if a.startswith("--steps=") or a.startswith("--warmup=") or a.startswith("--dump-outputs="):
             continue
         child_args.append(a)
     means = {}

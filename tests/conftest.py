@@ -7,8 +7,10 @@ import pytest
 # device (the direct all-reduce): each stream needs a hardware queue of its own.  The HIP runtime multiplexes streams over 4 queues by
 # default and a queue starts its packets in order, so rank 0's all-reduce would wait for a rank-4 kernel queued behind it
 # (tools/probes/world8_queues_probe.py).  Read once, when the runtime starts -- hence here, before anything loads it.  One rank per
-# device (the product's deployment: one host thread or process per GPU) never needs this.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
+# device (the product's deployment: one host thread or process per GPU) never needs this.  A smaller value inherited from the
+# environment (a launcher may set the runtime's default of 4) is raised, not kept: the world-8 tests would time out waiting on a peer.
+if int(os.environ.get("GPU_MAX_HW_QUEUES") or 0) < 16:
+    os.environ["GPU_MAX_HW_QUEUES"] = "16"
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

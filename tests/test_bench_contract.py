@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -66,7 +67,7 @@ def test_bench_py_prints_one_json_line(gpu):
     """the headline on a short schedule, with the CPU leg: the line's fields, the north_star fraction, and the check of what the timed
     region wrote against the oracle"""
     env = dict(os.environ, ATOMA_BENCH_CPU_THREADS="8")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "5", "--warmup", "2", "--no-extra", "--no-traffic", "--cpu-sample-seqs", "4"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "5", "--warmup", "2", "--no-extra", "--no-traffic", "--cpu-sample-seqs", "4"],
                          capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -78,6 +79,30 @@ def test_bench_py_prints_one_json_line(gpu):
     assert "G=4" in d["roofline"]["kernel"]
     v = d["verified"]
     assert v["ok"] is True and v["sequences"] == 4 and v["max_err"] < 0.05
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_the_headline_only_and_dumps_its_output(gpu, tmp_path):
+    """without --full: the headline line and nothing beside it; --dump-outputs writes what the last timed step computed, the same
+    bytes from run to run (seeded inputs) and the same as the --full run's output, which that run checks against the oracle"""
+    def run(name, *extra):
+        d = tmp_path / name
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "1", "--dump-outputs", str(d)] + list(extra),
+                           capture_output=True, text=True, timeout=600, env=dict(os.environ, ATOMA_BENCH_CPU_THREADS="8"))
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        return json.loads(lines[0]), np.load(d / "attn_out.npy")
+
+    d, o = run("a")
+    check_line(d, full=False)
+    assert d["steps"] == 7 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert not {"extra", "cpu_baseline", "verified", "decode_tokens_per_s_per_gpu"} & set(d), sorted(d)
+    assert o.dtype == np.float32 and o.shape == (256, 1, 32, 128) and np.isfinite(o).all() and (o != 0).any()
+    _, o2 = run("b")
+    assert np.array_equal(o, o2)
+    df, of = run("full", "--full", "--no-extra", "--no-traffic", "--cpu-sample-seqs", "4")
+    assert df["verified"]["ok"] is True and np.array_equal(o, of)
 
 
 @pytest.mark.gpu

@@ -19,7 +19,7 @@ def test_bench_ranks_on_one_device(gpu, world):
     env = dict(os.environ, ATOMA_BENCH_ONE_DEVICE="1", ATOMA_BENCH_TP_SMALL="1", ATOMA_XGMI_TIMEOUT_MS="30000", ATOMA_BENCH_EXTRA_TIMEOUT="300",
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1", "--master-port", str(29533 + world),
-           os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", "32", "--seq", "1024", "--no-traffic"]
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", "32", "--seq", "1024", "--no-traffic"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and lines, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
@@ -47,7 +47,7 @@ def test_bench_one_rank_through_the_rccl_communicator(gpu):
     communicator builds on request), ranks counted through it -- the part of the 8-GPU run's plumbing that RCCL lets a 1-GPU box execute."""
     env = dict(os.environ, ATOMA_BENCH_FORCE_COMM="1", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29547",
                HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "32", "--seq", "1024", "--no-traffic", "--no-extra",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "32", "--seq", "1024", "--no-traffic", "--no-extra",
            "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

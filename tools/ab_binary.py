@@ -34,7 +34,7 @@ def build(sha):
 
 def run_bench(lib, bench_args, traffic):
     env = dict(os.environ, ATOMA_HIP_LIB=os.path.abspath(lib))
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-extra", "--no-cpu-baseline"] + ([] if traffic else ["--no-traffic"]) + bench_args
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-extra", "--no-cpu-baseline"] + (["--full"] if traffic else ["--no-traffic"]) + bench_args
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if r.returncode != 0 or not lines:

@@ -3,7 +3,7 @@
 #   gpurun --timeout 1800 -- 'bash tools/gpu_call.sh r06 tests bench stats pmc'
 # usage: tools/gpu_call.sh TAG STEP [STEP ...]        outputs under gpurun_out/TAG/ (copy what should be judged into profiles/)
 #   tests[:K_EXPR]     pytest -m gpu (optionally -k K_EXPR)
-#   bench              the driver's line: python bench.py                      -> bench.json
+#   bench              the driver's line with everything beside it: python bench.py --full   -> bench.json
 #   stats              rocprofv3 --kernel-trace --stats of the headline        -> kernel_stats/
 #   pmc                FETCH_SIZE / WRITE_SIZE passes of the headline          -> pmc_fetch/ pmc_write/
 #   step[:own|vendor]  per-kernel breakdown of the configs[2] decode step      -> step_breakdown_b256_<which>.json
@@ -21,7 +21,7 @@ for step in "$@"; do
   echo "== $step"
   case $name in
     tests) (timeout 1700 python -m pytest tests -m gpu -q --tb=short ${arg:+-k "$arg"} 2>&1 | tail -40) > "$O/pytest_gpu.log"; tail -3 "$O/pytest_gpu.log" ;;
-    bench) timeout 900 python bench.py > "$O/bench.json" 2> "$O/bench.err"; tail -c 600 "$O/bench.json" ;;
+    bench) timeout 900 python bench.py --full > "$O/bench.json" 2> "$O/bench.err"; tail -c 600 "$O/bench.json" ;;
     stats) (cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/kernel_stats" -o decode -- python "$REPO/bench.py" --steps 30 --warmup 5 --no-cpu-baseline --no-extra --no-traffic > "$O/stats.log" 2>&1) ;;
     pmc) for c in FETCH_SIZE WRITE_SIZE; do (cd /tmp && timeout 300 rocprofv3 --pmc $c --output-format csv -d "$O/pmc_$c" -o decode -- python "$REPO/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --no-extra --no-traffic > "$O/pmc_$c.log" 2>&1); done ;;
     step) which=${arg:-own}; mb=256; [[ $which == vendor ]] && mb=128
