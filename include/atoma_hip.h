@@ -261,6 +261,33 @@ int atoma_linear_decode_residual(const void *x, const void *w, const void *resid
 int atoma_linear_decode_silu_mul(const void *x, const void *w_gate_up, void *y, int64_t batch, int64_t in_features, int64_t intermediate,
                                  int64_t x_row_stride, int64_t w_row_stride, int64_t y_row_stride, int dtype, void *stream);
 
+/* fp8 (OCP e4m3fn) WEIGHTS for the projections above, "W8A16" (no counterpart in the reference beyond its roadmap item "quantization"; the
+ * weight-side sibling of the fp8 KV cache): w8 [out_features, in_features] one byte per element (the nn.Linear layout), w_scale f32
+ * [out_features]; the value of a weight is e4m3(w8[n][k]) * w_scale[n]; activations, residuals and outputs stay f16 / bf16 (dtype).
+ *   y[b][n] = round_dtype(w_scale[n] * sum_k x[b][k] * e4m3(w8[n][k]))     fp32 accumulation, the scale applied once per output, one rounding
+ * The kernels stream half the bytes of the 16-bit ones and convert in registers (exact).  batch in [0, 64] (more is an error: the 65..256-row
+ * and prefill-sized products, the fused RMSNorm and the fused q/k/v + RoPE + cache forms exist for 16-bit weights only); in_features % 128
+ * == 0, out_features % 16 == 0 (% 32 for _silu_mul); x / y / residual row strides in elements, w8_row_stride in BYTES, a multiple of 16;
+ * w8 16-byte aligned, w_scale 4-byte aligned.  _residual and _silu_mul keep the rounding points of atoma_linear_decode_residual /
+ * _silu_mul (w_scale covers the stacked gate rows, then the up rows) and are bit-identical to the plain call followed by atoma_add /
+ * atoma_silu_mul.  A NaN byte (0x7f / 0xff) in a weight row makes that output column NaN and no other. */
+int atoma_linear_decode_fp8w(const void *x, const void *w8, const float *w_scale, void *y, int64_t batch, int64_t in_features,
+                             int64_t out_features, int64_t x_row_stride, int64_t w8_row_stride, int64_t y_row_stride, int dtype, void *stream);
+int atoma_linear_decode_fp8w_residual(const void *x, const void *w8, const float *w_scale, const void *residual, void *y, int64_t batch,
+                                      int64_t in_features, int64_t out_features, int64_t x_row_stride, int64_t w8_row_stride,
+                                      int64_t residual_row_stride, int64_t y_row_stride, int dtype, void *stream);
+int atoma_linear_decode_fp8w_silu_mul(const void *x, const void *w8_gate_up, const float *w_scale, void *y, int64_t batch, int64_t in_features,
+                                      int64_t intermediate, int64_t x_row_stride, int64_t w8_row_stride, int64_t y_row_stride, int dtype,
+                                      void *stream);
+
+/* 16-bit weights -> the fp8 form above, on the device, one pass per output row: amax = max |f32(w)|, scale_out[n] = amax / 448 in f32 (1.0 for
+ * an all-zero row), w8_out = e4m3fn(clamp(f32(w) * (f32(1) / scale), -448, 448)), round to nearest even, saturating -- the arithmetic of
+ * atoma_reshape_and_cache_flash_fp8.  w [out_features, in_features] of dtype, w_row_stride in elements (% 8), w8_row_stride in bytes (% 16),
+ * in_features % 16 == 0, w and w8_out 16-byte aligned.  Stream-ordered, no host synchronisation.  Pre-quantised checkpoints skip it and
+ * pass their own bytes and scales. */
+int atoma_quantize_weight_fp8(const void *w, int64_t out_features, int64_t in_features, int64_t w_row_stride, int dtype, void *w8_out,
+                              int64_t w8_row_stride, float *scale_out, void *stream);
+
 /* The RMSNorm in FRONT of a projection folded into it (llama.rs:402 -> 269-271 for q/k/v, :408 -> 364-365 for gate/up):
  * y = rms_norm(x; norm_weight, eps) . w^T, and the _silu_mul form of the stacked gate/up projection on top of that.  On the rows the
  * VALU streaming kernel serves (1 by default, ATOMA_LINEAR_GEMV_MAX_BATCH up to 2) the projection kernel derives each row's scale itself with atoma_rms_norm's own arithmetic and

@@ -380,6 +380,112 @@ def bench_linear():
         w.free()
 
 
+def bench_linear_fp8w():
+    """fp8 weights against 16-bit weights, the five Llama-3.1-8B projection shapes x batch 1, 4, 8, 16, 64: atoma_linear_decode_fp8w timed
+    interleaved with atoma_linear_decode on 16-bit weights of the same shape in the same process, three repeats.  Both rotate through enough
+    weight copies (> 600 MB per set) that no call finds its weights in the 256 MB Infinity Cache.  fp8 bytes = N.K + 4.N + 2.B.K + 2.B.N.
+    ATOMA_BENCH_FP8W_OUT=path: the whole table as one JSON document (profiles/fp8w_linear.json); also runs the 8B step at batch 1 and 16."""
+    rng = np.random.default_rng(8)
+    rows, repeats = [], 3
+    only = [t for t in os.environ.get("ATOMA_BENCH_FP8W_SHAPES", "").split(",") if t]        # e.g. "gate_up,down": a subset, for a kernel trace
+    batches = tuple(int(t) for t in os.environ.get("ATOMA_BENCH_FP8W_BATCHES", "1,4,8,16,64").split(","))
+    for name, N, K in (("qkv", 6144, 4096), ("o", 4096, 4096), ("gate_up", 28672, 4096), ("down", 4096, 14336), ("lm_head", 128256, 4096)):
+        if only and name not in only:
+            continue
+        copies = max(2, -(-(600 << 20) // (N * K)))
+        w16, w8, sc = [], [], []
+        for i in range(copies):
+            w16.append(rand_dev(rng, N * K * 2))
+            w8.append(ah.DeviceBuffer(N * K)); sc.append(ah.DeviceBuffer(N * 4))
+            assert ah.lib.atoma_quantize_weight_fp8(w16[i].ptr, N, K, K, 1, w8[i].ptr, K, sc[i].ptr, None) == 0, ah.last_error()
+        ah.synchronize()
+        for B in batches:
+            x, y = rand_dev(rng, B * K * 2), ah.DeviceBuffer(B * N * 2)
+            turn = [0]
+
+            def f8():
+                i = turn[0] = (turn[0] + 1) % copies
+                ah.lib.atoma_linear_decode_fp8w(x.ptr, w8[i].ptr, sc[i].ptr, y.ptr, B, K, N, K, K, N, 1, None)
+
+            def f16():
+                i = turn[0] = (turn[0] + 1) % copies
+                ah.lib.atoma_linear_decode(x.ptr, w16[i].ptr, y.ptr, B, K, N, K, K, N, 1, None)
+            t8, t16 = [], []
+            for _ in range(repeats):
+                t8.append(timeit(f8, iters=2 * copies if copies > 10 else 20))
+                t16.append(timeit(f16, iters=2 * copies if copies > 10 else 20))
+            m8, m16 = float(np.median(t8)), float(np.median(t16))
+            nbytes = N * K + 4 * N + 2 * B * K + 2 * B * N
+            rec = dict(shape=name, N=N, K=K, batch=B, fp8_ms=round(m8, 5), bf16_ms=round(m16, 5), speedup=round(m16 / m8, 3),
+                       fp8_ms_repeats=[round(t, 5) for t in t8], bf16_ms_repeats=[round(t, 5) for t in t16],
+                       spread=round(max((max(t8) - min(t8)) / m8, (max(t16) - min(t16)) / m16), 4),
+                       fp8_bytes=nbytes, fp8_frac_hbm=round(nbytes / (m8 * 1e-3) / 1e9 / HBM, 4),
+                       bf16_frac_hbm=round((2 * N * K + 2 * B * K + 2 * B * N) / (m16 * 1e-3) / 1e9 / HBM, 4), weight_copies=copies)
+            rows.append(rec)
+            print(json.dumps(dict(workload=f"L5 linear_decode_fp8w vs 16-bit {name} [{N} x {K}] batch={B}", **rec)), flush=True)
+        for b in w16 + w8 + sc:
+            b.free()
+    out = os.environ.get("ATOMA_BENCH_FP8W_OUT")
+    if out:
+        steps = bench_step_fp8w()
+        doc = dict(command="ATOMA_BENCH_FP8W_OUT=<this file> python tools/bench_kernels.py linear_fp8w", device="MI355X", hbm_peak_GBps=HBM,
+                   note="times in ms, median of 3 interleaved repeats; spread = (max - min) / median of the repeats, the larger of the two sides; "
+                        "rotating weights (no call finds its weights in the Infinity Cache); step = hipGraph replay of tools/decode_step.py",
+                   linear=rows, step=steps)
+        with open(out, "w") as f:
+            json.dump(doc, f, indent=1)
+
+
+def bench_step_fp8w():
+    """The Llama-3.1-8B decode step (context 4096, hipGraph replay) at batch 1 and 16: 16-bit weights against weight_dtype="fp8", same process."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import decode_step as DS
+    rng = np.random.default_rng(9)
+    c = DS.LLAMA_3_1_8B
+    cos, sin = DS.rope_tables(c)
+    w = dict(emb=rand_dev(rng, c.vocab * c.hidden * 2), lm_head=rand_dev(rng, c.vocab * c.hidden * 2),
+             norm_f=rand_dev(rng, c.hidden * 2), cos=ah.DeviceBuffer.from_numpy(cos), sin=ah.DeviceBuffer.from_numpy(sin),
+             norm1=[rand_dev(rng, c.hidden * 2) for _ in range(c.layers)], norm2=[rand_dev(rng, c.hidden * 2) for _ in range(c.layers)],
+             wqkv=[rand_dev(rng, c.qkv * c.hidden * 2) for _ in range(c.layers)], wo=[rand_dev(rng, c.hidden * c.h * c.d * 2) for _ in range(c.layers)],
+             wgu=[rand_dev(rng, 2 * c.inter * c.hidden * 2) for _ in range(c.layers)], wdown=[rand_dev(rng, c.hidden * c.inter * 2) for _ in range(c.layers)])
+    st, S, out = ah.Stream(), 4096, []
+    for B in (1, 16):
+        pps = S // c.page + 1
+        bt = rng.permutation(B * pps).astype(np.int32).reshape(B, pps)
+        ctx = np.full(B, S)
+        slots = bt[np.arange(B), ctx // c.page].astype(np.int64) * c.page + ctx % c.page
+        ids = rng.integers(0, c.vocab, B)
+        graphs, steps = {}, {}
+        for wd in ("bf16", "fp8"):
+            step = steps[wd] = DS.DecodeStep(c, B, B * pps + 2, pps, w, st, fused_epilogues=True, weight_dtype=wd)
+            step.set_inputs(ids, ctx, slots, ctx + 1, bt)
+            step.run(); st.synchronize()
+            with ah.Graph.capture(st) as g:
+                step.run()
+            graphs[wd] = g
+        times = {"bf16": [], "fp8": []}
+        for _ in range(3):
+            for wd in ("bf16", "fp8"):
+                g = graphs[wd]
+                for _ in range(3):
+                    g.launch()
+                st.synchronize()
+                a, b = ah.Event(), ah.Event()
+                a.record(st.s)
+                for _ in range(10):
+                    g.launch()
+                b.record(st.s)
+                b.synchronize()
+                times[wd].append(a.elapsed_ms(b) / 10)
+        m16, m8 = float(np.median(times["bf16"])), float(np.median(times["fp8"]))
+        rec = dict(batch=B, context=S, bf16_step_ms=round(m16, 4), fp8_step_ms=round(m8, 4), speedup=round(m16 / m8, 3),
+                   bf16_step_ms_repeats=[round(t, 4) for t in times["bf16"]], fp8_step_ms_repeats=[round(t, 4) for t in times["fp8"]])
+        out.append(rec)
+        print(json.dumps(dict(workload=f"E2 Llama-3.1-8B decode step, 16-bit vs fp8 weights, batch={B}", **rec)), flush=True)
+        del steps, graphs
+    return out
+
+
 def bench_linear_mid():
     """f.1 at 17..64 rows: atoma_linear_decode (linear_mid_kernel: x staged through LDS once per workgroup) against the vendor
     GEMM (atoma_linear above ATOMA_LINEAR_STREAM_MAX_BATCH) on the Llama-3.1-8B layer shapes and on the shapes of one rank of a

@@ -5,7 +5,8 @@ The op sequence is the reference's `Llama::forward` for decode tokens (models/sr
 KV-cache write -> paged decode attention -> o projection -> residual -> RMSNorm -> gate/up projection -> SiLU.up ->
 down projection -> residual] -> RMSNorm -> lm_head -> argmax.  q/k/v and gate/up weights are stored concatenated
 (row blocks of one matrix), which changes nothing in the arithmetic: every output row is an independent dot product.
-Projections: atoma_linear (weight streaming up to 4 rows, hipBLASLt above).  Everything is enqueued on one stream, so a step can be captured in a hipGraph.
+Projections: atoma_linear (weight streaming up to 4 rows, hipBLASLt above), or, with weight_dtype="fp8" (batch <= 64), fp8 weights
+quantised once at upload and atoma_linear_decode_fp8w[_residual / _silu_mul].  Everything is enqueued on one stream, so a step can be captured in a hipGraph.
 """
 import os
 import sys
@@ -34,13 +35,23 @@ class DecodeStep:
     """Device-resident weights, caches and activations of a model + `run()` = one decode step for `batch` sequences."""
 
     def __init__(self, cfg, batch, num_pages, max_blocks, weights, stream, keep_intermediates=False, fused_epilogues=False, fuse_norm=True,
-                 allreduce=None, kv_fp8=False, kv_scale=0.05, own_projections=False, allreduce_norm=None):
+                 allreduce=None, kv_fp8=False, kv_scale=0.05, own_projections=False, allreduce_norm=None, weight_dtype="bf16"):
         """allreduce(ptr, count): in-place sum of a [batch, hidden] bf16 tensor over the tensor-parallel ranks, enqueued on
         `stream` -- called after the o and the down projection when `cfg` / `weights` are ONE rank's shard
         (llama_nccl.rs:139,195 via TensorParallelRowLinear, multi_gpu.rs:48-50); None = not tensor parallel."""
         c = self.cfg = cfg
         self.B, self.stream, self.keep = batch, stream, keep_intermediates
         self.allreduce = allreduce
+        # weight_dtype="fp8": the q/k/v, o, gate/up and down weights as e4m3fn bytes with one f32 scale per output row, quantised ONCE here
+        # (atoma_quantize_weight_fp8) and multiplied by atoma_linear_decode_fp8w[_residual / _silu_mul]; lm_head and the embedding stay 16-bit.
+        # The fused-RMSNorm and fused q/k/v + RoPE + cache forms do not exist over fp8 weights: the norms and atoma_rope_qk_cache run on their own.
+        if weight_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"DecodeStep: weight_dtype must be 'bf16' or 'fp8', not {weight_dtype!r}")
+        self.fp8w = weight_dtype == "fp8"
+        if self.fp8w and batch > 64:
+            raise ValueError(f"DecodeStep(weight_dtype='fp8'): batch {batch} > 64 -- the fp8-weight projections serve at most 64 rows")
+        if self.fp8w and allreduce is not None:
+            raise ValueError("DecodeStep(weight_dtype='fp8'): tensor-parallel ranks are not supported with fp8 weights")
         # allreduce_norm(in, residual, weight, x_out, norm_out, rows) -> True when it enqueued "x_out = residual + allreduce(in); norm_out =
         # RMSNorm(x_out) * weight" as ONE launch (atoma_xgmi_allreduce_add_rms_norm / atoma_allreduce_add_rms_norm); False = not available now:
         # the step falls back to allreduce + atoma_add_rms_norm (same bits)
@@ -64,6 +75,18 @@ class DecodeStep:
         self.norm_in_proj = os.environ.get("ATOMA_STEP_NORM_IN_PROJ", "1") != "0"   # fused path: RMSNorm inside the q/k/v and gate/up projections (A/B switch)
         self.fuse_norm = fuse_norm and not keep_intermediates and not self.fused   # residual add + the RMSNorm that follows it in one kernel
         self.w = weights                                   # dict of DeviceBuffers, see random_weights / upload_weights
+        self.w8, self.w8_scale = {}, {}                    # fp8w: name -> per-layer DeviceBuffers (bytes [N, K]; f32 [N])
+        if self.fp8w:
+            self.qkv_fused = self.norm_in_proj = False
+            shapes = dict(wqkv=(c.qkv, c.hidden), wo=(c.hidden, c.h * c.d), wgu=(2 * c.inter, c.hidden), wdown=(c.hidden, c.inter))
+            for name, (n, k) in shapes.items():
+                self.w8[name], self.w8_scale[name] = [], []
+                for l in range(c.layers):
+                    w8, sc = ah.DeviceBuffer(n * k), ah.DeviceBuffer(n * 4)
+                    self._ok(ah.lib.atoma_quantize_weight_fp8(weights[name][l].ptr, n, k, k, BF16, w8.ptr, k, sc.ptr, stream.s), f"quantising {name}[{l}]")
+                    self.w8[name].append(w8)
+                    self.w8_scale[name].append(sc)
+            stream.synchronize()
         page_elems = c.page * c.hk * c.d
         # kv_fp8: the KV cache holds e4m3fn bytes with one dequantisation scale per kv head (atoma_rope_qk_cache_fp8 /
         # atoma_paged_decode_fp8); everything else of the step is unchanged
@@ -115,6 +138,14 @@ class DecodeStep:
         if rc != 0:
             raise RuntimeError(f"{what}: {ah.last_error()}")
 
+    def _proj(self, name, l, x, y, K, N, what):
+        """y [B, N] = x [B, K] . w[name][l]^T through the step's projection entry (fp8 or 16-bit weights)."""
+        B, s = self.B, self.stream.s
+        if self.fp8w:
+            self._ok(ah.lib.atoma_linear_decode_fp8w(x.ptr, self.w8[name][l].ptr, self.w8_scale[name][l].ptr, y.ptr, B, K, N, K, K, N, BF16, s), what)
+        else:
+            self._ok(self.linear(x.ptr, self.w[name][l].ptr, y.ptr, B, K, N, K, K, N, BF16, s), what)
+
     def run(self):
         c, B, s, L = self.cfg, self.B, self.stream.s, ah.lib
         H, qkvw, hd = c.hidden, c.qkv, c.h * c.d
@@ -139,7 +170,7 @@ class DecodeStep:
             else:
                 if not (self.fuse_norm and l > 0):         # with fuse_norm the previous layer's last add produced xn already
                     self._ok(L.atoma_rms_norm(x.ptr, self.w["norm1"][l].ptr, xn.ptr, B, H, H, H, c.eps, BF16, s), "rms_norm")
-                self._ok(self.linear(xn.ptr, self.w["wqkv"][l].ptr, qkv.ptr, B, H, qkvw, H, H, qkvw, BF16, s), "qkv projection")
+                self._proj("wqkv", l, xn, qkv, H, qkvw, "qkv projection")
             qkv_pre = None
             if self.keep:                                   # RoPE works in place: keep the projection's output for the checker
                 qkv_pre = self._buf("qkv_pre", l, B * qkvw * 2)
@@ -171,7 +202,13 @@ class DecodeStep:
             # ping-pong the residual stream so that no kernel reads and writes the same buffer
             x2 = self._buf("x2", l, B * H * 2) if self.keep else self._buf("x2a" if l % 2 == 0 else "x2b", 0, B * H * 2)
             o = gu = dn = None
-            if self.fused:
+            if self.fused and self.fp8w:
+                w8, sc = self.w8, self.w8_scale
+                self._ok(L.atoma_linear_decode_fp8w_residual(att.ptr, w8["wo"][l].ptr, sc["wo"][l].ptr, x.ptr, x1.ptr, B, hd, H, hd, hd, H, H, BF16, s), "o projection + residual")
+                self._ok(L.atoma_rms_norm(x1.ptr, self.w["norm2"][l].ptr, xn2.ptr, B, H, H, H, c.eps, BF16, s), "rms_norm")
+                self._ok(L.atoma_linear_decode_fp8w_silu_mul(xn2.ptr, w8["wgu"][l].ptr, sc["wgu"][l].ptr, act.ptr, B, H, c.inter, H, H, c.inter, BF16, s), "gate/up projection + silu * up")
+                self._ok(L.atoma_linear_decode_fp8w_residual(act.ptr, w8["wdown"][l].ptr, sc["wdown"][l].ptr, x1.ptr, x2.ptr, B, c.inter, H, c.inter, c.inter, H, H, BF16, s), "down projection + residual")
+            elif self.fused:
                 self._ok(L.atoma_linear_decode_residual(att.ptr, self.w["wo"][l].ptr, x.ptr, x1.ptr, B, hd, H, hd, hd, H, H, BF16, s), "o projection + residual")
                 if self.norm_in_proj:
                     self._ok(L.atoma_linear_decode_rmsnorm_silu_mul(x1.ptr, self.w["norm2"][l].ptr, c.eps, self.w["wgu"][l].ptr, act.ptr, xn2.ptr, B, H, c.inter,
@@ -182,7 +219,7 @@ class DecodeStep:
                 self._ok(L.atoma_linear_decode_residual(act.ptr, self.w["wdown"][l].ptr, x1.ptr, x2.ptr, B, c.inter, H, c.inter, c.inter, H, H, BF16, s), "down projection + residual")
             else:
                 o = self._buf("o", l, B * H * 2)
-                self._ok(self.linear(att.ptr, self.w["wo"][l].ptr, o.ptr, B, hd, H, hd, hd, H, BF16, s), "o projection")
+                self._proj("wo", l, att, o, hd, H, "o projection")
                 # all-reduce + residual add + RMSNorm in the all-reduce's own launch where the engine offers it, else the two calls (same bits)
                 one = bool(self.fuse_norm and self.allreduce_norm and self.allreduce_norm(o.ptr, x.ptr, self.w["norm2"][l].ptr, x1.ptr, xn2.ptr, B))
                 if not one and self.allreduce:
@@ -198,10 +235,10 @@ class DecodeStep:
                     self._ok(L.atoma_linear_decode_silu_mul(xn2.ptr, self.w["wgu"][l].ptr, act.ptr, B, H, c.inter, H, H, c.inter, BF16, s), "gate/up projection + silu * up")
                 else:
                     gu = self._buf("gu", l, B * 2 * c.inter * 2)
-                    self._ok(self.linear(xn2.ptr, self.w["wgu"][l].ptr, gu.ptr, B, H, 2 * c.inter, H, H, 2 * c.inter, BF16, s), "gate/up projection")
+                    self._proj("wgu", l, xn2, gu, H, 2 * c.inter, "gate/up projection")
                     self._ok(L.atoma_silu_mul(gu.ptr, gu.ptr + c.inter * 2, act.ptr, B, c.inter, 2 * c.inter, 2 * c.inter, c.inter, BF16, s), "silu * up")
                 dn = self._buf("dn", l, B * H * 2)
-                self._ok(self.linear(act.ptr, self.w["wdown"][l].ptr, dn.ptr, B, c.inter, H, c.inter, c.inter, H, BF16, s), "down projection")
+                self._proj("wdown", l, act, dn, c.inter, H, "down projection")
                 last = l == c.layers - 1
                 nw, nout = (self.w["norm_f"], xf) if last else (self.w["norm1"][l + 1], self._buf("xn1", l + 1, B * H * 2))
                 one = bool(self.fuse_norm and self.allreduce_norm and self.allreduce_norm(dn.ptr, x1.ptr, nw.ptr, x2.ptr, nout.ptr, B))
