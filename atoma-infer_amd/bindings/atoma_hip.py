@@ -104,6 +104,17 @@ lib.atoma_num_cus.argtypes = [_int]
 lib.atoma_num_cus.restype = _int
 
 
+class SamplingParams(C.Structure):
+    """atoma_sampling_params (include/atoma_hip.h): one per row of atoma_sample_batch, on the device; 32 bytes."""
+    _fields_ = [("mode", C.c_int32), ("temperature", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float),
+                ("repetition_penalty", C.c_float), ("repeat_last_n", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+# numpy view of the same layout: np.zeros(rows, SAMPLING_PARAMS_DTYPE) uploads as the `params` argument
+SAMPLING_PARAMS_DTYPE = np.dtype([("mode", "<i4"), ("temperature", "<f4"), ("top_k", "<i4"), ("top_p", "<f4"),
+                                  ("repetition_penalty", "<f4"), ("repeat_last_n", "<i4"), ("reserved", "<i4", (2,))])
+
+
 def _opt(name, argtypes, restype=_int):
     """Entry points added later in the round: bind when present."""
     if hasattr(lib, name):
@@ -143,6 +154,9 @@ _opt("atoma_linear", [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _
 _opt("atoma_topk_rows", [_vp, _i64, _i64, _i64, _int, _i64, _vp, _vp, _vp])
 _opt("atoma_sample_rows", [_vp, _i64, _i64, _i64, _int, _f32, _i64, _f32, _vp, _vp, _vp, _vp])
 _opt("atoma_argmax_rows", [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp])
+
+# logits, rows, vocab, row_stride, dtype, params, u, history, history_stride, history_len, append, eos_ids, num_eos, out_idx, out_logit, out_stop, stream
+_opt("atoma_sample_batch", [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _i64, _vp, _int, _vp, _i64, _vp, _vp, _vp, _vp])
 _opt("atoma_rope_table", [_vp, _vp, _i64, _i64, _f32, _f32, _f32, _f32, _i64, _int])
 _opt("atoma_reshape_and_cache_flash_fp8", [_vp, _vp, _vp, _vp, _i64p, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp])
 _opt("atoma_rope_qk_cache_fp8", [_vp, _vp, _vp, _vp, _vp, _i64p, _vp, _vp, _vp, _vp, _i64p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _vp])

@@ -344,6 +344,39 @@ int atoma_topk_rows(const void *logits, int64_t rows, int64_t vocab, int64_t row
 int atoma_sample_rows(const void *logits, int64_t rows, int64_t vocab, int64_t row_stride, int dtype, float temperature, int64_t top_k,
                       float top_p, const float *u, int32_t *out_idx, float *out_logit, void *stream);
 
+/* Per-request sampling of a whole step in ONE call: what backends/vllm/src/model_executor.rs:173-278 does per sequence group
+ * (its own LogitsProcessor mode / temperature / k / p from llm_service.rs:346-372, its own repetition penalty over the tail of
+ * its token ids :211-225, the log-prob read from the penalised row :249, the EOS test :237-241).  Every per-row setting is in
+ * device memory, so a captured graph replays with new settings; the call launches two kernels whatever `rows` and the mix of
+ * settings are, does no host synchronisation and keeps no state but the stream's workspace (run it once eagerly, or reserve
+ * rows * min(vocab, 1024) * 8 bytes with atoma_reserve_workspace, before capturing it).
+ * Per row r, with x_i = f32(logits[r, i]):
+ *   1. penalty (repetition_penalty != 1 and a history is given): for every distinct token t with 0 <= t < vocab among the last
+ *      min(history_len[r], repeat_last_n) entries of history[r]:  x_t = x_t >= 0 ? x_t / penalty : x_t * penalty  (one correctly
+ *      rounded f32 operation, once per token however often it occurs: candle's apply_repeat_penalty).  NaN stays NaN, -inf stays
+ *      -inf.  The logits buffer is not modified.
+ *   2. mode 0: the argmax of x by atoma_argmax_rows' rule.  mode 1: atoma_sample_rows' draw on x with the row's temperature,
+ *      top_k, top_p and u[r].
+ *   3. out_logit[r] (optional) = x[token], the penalised value; out_stop[r] (optional) = 1 iff the token is one of eos_ids.
+ *   4. append = 1: the token is written at history[r, history_len[r]] and history_len[r] incremented when history_len[r] <
+ *      history_stride; a full row is left as it is.
+ *   5. a row with invalid parameters (mode not 0 / 1; mode 1 with temperature <= 0 or NaN, top_k outside [0, 1024] or top_p
+ *      outside (0, 1]; penalty on with repeat_last_n <= 0; reserved not 0) gets out_idx[r] = -1, out_stop[r] = 0 and no append; the other rows
+ *      are unaffected.
+ * vocab <= 2 M; with a history (the penalty's bitmap of seen tokens lives in LDS) vocab <= 262144.  num_eos in [0, 16]. */
+typedef struct atoma_sampling_params {   /* one per row, on the device; 32 bytes, no padding */
+    int32_t mode;               /* 0 = greedy (ArgMax), 1 = stochastic (All / TopK / TopP / TopKThenTopP by top_k, top_p) */
+    float temperature;          /* stochastic: > 0 (+inf is taken as it is: the uniform distribution over the kept tokens) */
+    int32_t top_k;              /* 0 = off, else [1, 1024] */
+    float top_p;                /* (0, 1], 1 = off */
+    float repetition_penalty;   /* 1 = off; the reference admits (0, 2] */
+    int32_t repeat_last_n;      /* the penalty ranges over the last n tokens of the row's history; > 0 when the penalty is on */
+    int32_t reserved[2];        /* must be 0: a row with anything else here is invalid */
+} atoma_sampling_params;
+int atoma_sample_batch(const void *logits, int64_t rows, int64_t vocab, int64_t row_stride, int dtype, const atoma_sampling_params *params,
+                       const float *u, int32_t *history, int64_t history_stride, int32_t *history_len, int append, const int32_t *eos_ids,
+                       int64_t num_eos, int32_t *out_idx, float *out_logit, uint8_t *out_stop, void *stream);
+
 /* Tensor-parallel sum all-reduce (models/src/multi_gpu.rs:141-179 `AllReduce::cuda_fwd`,
  * bootstrap backends/vllm/src/model_executor.rs:413,436-439 `Id::new` / `Comm::from_rank`).
  * One process (or thread) per GPU over RCCL/xGMI.  id128: 128-byte ncclUniqueId. */

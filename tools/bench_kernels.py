@@ -308,6 +308,116 @@ def bench_sampling():
              note="algorithmic bytes = one read of the logits; the kernel reads them twice (second pass from MALL / L2)")
 
 
+def bench_sample_batch():
+    """atoma_sample_batch at the BASELINE batch (256 x 128256 bf16 logits), three legs interleaved in one process, median of 3 repeats, logits
+    rotating through 6 copies (394 MB: no call finds its rows in the 256 MB Infinity Cache):
+      (a) the mixed batch of tests/test_sample_batch_gpu.py (row r: greedy / All / top-k 1, 50, 1024 / top-p 0.5, 0.9 / top-k 50 + top-p 0.9,
+          temperatures 0.7 / 1 / 2: 22 distinct parameter sets) WITHOUT penalties on the batch-uniform entry points: one atoma_argmax_rows /
+          atoma_sample_rows call per parameter set on rows already gathered by set (the gather copy itself is not charged), and one per row;
+      (b) the same batch in one atoma_sample_batch call, without and with the penalties of that test (half of the rows, histories of 1..2048);
+      (c) an all-greedy batch without penalties: atoma_argmax_rows against atoma_sample_batch;
+      (t) every row top-k 50 at temperature 0.8 (the one-pass register top-k): atoma_sample_rows against atoma_sample_batch without and with
+          the penalties.
+    ATOMA_BENCH_SAMPLE_BATCH_OUT=path: the table as one JSON document (profiles/sample_batch.json)."""
+    rng = np.random.default_rng(9)
+    B, vocab, copies, repeats, hstride = 256, 128256, 6, 3, 2056
+    logits = [rand_dev(rng, B * vocab * 2) for _ in range(copies)]
+    modes = [(0, 0, 1.0), (1, 0, 1.0), (1, 1, 1.0), (1, 50, 1.0), (1, 1024, 1.0), (1, 0, 0.5), (1, 0, 0.9), (1, 50, 0.9)]
+
+    def params(greedy=False, penalties=False, topk50=False):
+        a = np.zeros(B, ah.SAMPLING_PARAMS_DTYPE)
+        for r in range(B):
+            m, k, p = (1, 50, 1.0) if topk50 else modes[0 if greedy else r % 8]
+            pen = [0.8, 1.1, 1.3, 2.0][(r // 32) % 4] if penalties and (r // 8) % 2 else 1.0
+            a[r] = (m, 0.8 if topk50 else [0.7, 1.0, 2.0][(r // 16) % 3], k, p, pen, [64, 512, 4096][r % 3], (0, 0))
+        return a
+    mixed = params()
+    d_mixed, d_pen, d_greedy = (ah.DeviceBuffer.from_numpy(params(**kw)) for kw in (dict(), dict(penalties=True), dict(greedy=True)))
+    d_k50, d_k50_pen = (ah.DeviceBuffer.from_numpy(params(topk50=True, penalties=pp)) for pp in (False, True))
+    hist = rng.integers(0, vocab // 64, (B, hstride)).astype(np.int32)                  # a narrow id range: plenty of duplicates
+    hlen = np.array([1 + (r * 37) % 2048 if r else 2048 for r in range(B)], np.int32)
+    d_hist, d_hlen = ah.DeviceBuffer.from_numpy(hist), ah.DeviceBuffer.from_numpy(hlen)
+    u = ah.DeviceBuffer.from_numpy(rng.random(B).astype(np.float32))
+    idx, val, stop = ah.DeviceBuffer.zeros((B,), np.int32), ah.DeviceBuffer.zeros((B,), np.float32), ah.DeviceBuffer.zeros((B,), np.uint8)
+    eos = ah.DeviceBuffer.from_numpy(np.array([128001, 128009], np.int32))
+    # rows gathered by parameter set: [start, count, mode, temperature, k, p]
+    sets = {}
+    for r in range(B):
+        key = (0,) if mixed["mode"][r] == 0 else (1, float(mixed["temperature"][r]), int(mixed["top_k"][r]), float(mixed["top_p"][r]))
+        sets[key] = sets.get(key, 0) + 1
+    groups, start = [], 0
+    for key, n in sets.items():
+        groups.append((start, n, key))
+        start += n
+    turn = [0]
+
+    def nxt():
+        turn[0] = (turn[0] + 1) % copies
+        return logits[turn[0]].ptr
+
+    def old_call(base, r0, n, key):
+        off = r0 * vocab * 2
+        if key[0] == 0:
+            rc = ah.lib.atoma_argmax_rows(base + off, n, vocab, vocab, 1, idx.ptr + 4 * r0, val.ptr + 4 * r0, None)
+        else:
+            rc = ah.lib.atoma_sample_rows(base + off, n, vocab, vocab, 1, key[1], key[2], key[3], u.ptr + 4 * r0, idx.ptr + 4 * r0, val.ptr + 4 * r0, None)
+        assert rc == 0, ah.last_error()
+
+    def a_gathered():
+        base = nxt()
+        for r0, n, key in groups:
+            old_call(base, r0, n, key)
+
+    def a_per_row():
+        base = nxt()
+        for r in range(B):
+            old_call(base, r, 1, (0,) if mixed["mode"][r] == 0 else (1, float(mixed["temperature"][r]), int(mixed["top_k"][r]), float(mixed["top_p"][r])))
+
+    def new_call(prm, with_hist):
+        def f():
+            rc = ah.lib.atoma_sample_batch(nxt(), B, vocab, vocab, 1, prm.ptr, u.ptr, d_hist.ptr if with_hist else None, hstride if with_hist else 0,
+                                           d_hlen.ptr if with_hist else None, 0, eos.ptr, 2, idx.ptr, val.ptr, stop.ptr, None)
+            assert rc == 0, ah.last_error()
+        return f
+
+    def c_argmax():
+        assert ah.lib.atoma_argmax_rows(nxt(), B, vocab, vocab, 1, idx.ptr, val.ptr, None) == 0
+
+    def t_sample_rows():
+        assert ah.lib.atoma_sample_rows(nxt(), B, vocab, vocab, 1, 0.8, 50, 1.0, u.ptr, idx.ptr, val.ptr, None) == 0
+    legs = dict(a_gathered=a_gathered, a_per_row=a_per_row, b_new=new_call(d_mixed, False), b_new_penalties=new_call(d_pen, True),
+                c_argmax_rows=c_argmax, c_new_all_greedy=new_call(d_greedy, False), t_sample_rows_topk50=t_sample_rows,
+                t_new_topk50=new_call(d_k50, False), t_new_topk50_penalties=new_call(d_k50_pen, True))
+    only = [t for t in os.environ.get("ATOMA_BENCH_SAMPLE_BATCH_LEGS", "").split(",") if t]      # a subset, for a kernel trace
+    if only:
+        legs = {k: v for k, v in legs.items() if k in only}
+    times = {k: [] for k in legs}
+    for _ in range(repeats):
+        for k, f in legs.items():
+            times[k].append(timeit(f, iters=12))
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    nbytes = B * vocab * 2
+    for k in legs:
+        emit(f"S4 sample_batch {k} B={B} vocab={vocab} bf16", med[k], repeats=[round(t, 4) for t in times[k]], logits_bytes=nbytes,
+             logits_floor_ms=round(nbytes / (HBM * 1e9) * 1e3, 4))
+    out = os.environ.get("ATOMA_BENCH_SAMPLE_BATCH_OUT")
+    if out and not only:
+        ratio = lambda a, b: round(med[a] / med[b], 3)
+        doc = dict(command="ATOMA_BENCH_SAMPLE_BATCH_OUT=<this file> python tools/bench_kernels.py sample_batch", device="MI355X", hbm_peak_GBps=HBM,
+                   note="ms, median of 3 interleaved repeats of 12 calls; 256 x 128256 bf16 logits rotating through 6 copies; parameter sets of the "
+                        "mixed batch: %d; (a) runs the batch-uniform entry points without penalties (they have none)" % len(groups),
+                   ms={k: round(v, 4) for k, v in med.items()}, ms_repeats={k: [round(t, 4) for t in v] for k, v in times.items()},
+                   logits_bytes=nbytes, logits_floor_ms=round(nbytes / (HBM * 1e9) * 1e3, 4),
+                   ratios=dict(a_gathered_over_b_new=ratio("a_gathered", "b_new"), a_per_row_over_b_new=ratio("a_per_row", "b_new"),
+                               a_gathered_over_b_new_penalties=ratio("a_gathered", "b_new_penalties"),
+                               b_new_penalties_over_b_new=ratio("b_new_penalties", "b_new"),
+                               c_new_all_greedy_over_c_argmax_rows=ratio("c_new_all_greedy", "c_argmax_rows"),
+                               t_new_topk50_over_t_sample_rows_topk50=ratio("t_new_topk50", "t_sample_rows_topk50"),
+                               t_new_topk50_penalties_over_t_new_topk50=ratio("t_new_topk50_penalties", "t_new_topk50")))
+        with open(out, "w") as f:
+            json.dump(doc, f, indent=1)
+
+
 def bench_graph():
     """A decode step's attention-path kernels for 32 layers (RMSNorm, fused RoPE + cache write, paged decode) at small
     batch, launched eagerly and replayed from a hipGraph: the launch-bound end of the path."""

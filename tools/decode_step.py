@@ -35,8 +35,12 @@ class DecodeStep:
     """Device-resident weights, caches and activations of a model + `run()` = one decode step for `batch` sequences."""
 
     def __init__(self, cfg, batch, num_pages, max_blocks, weights, stream, keep_intermediates=False, fused_epilogues=False, fuse_norm=True,
-                 allreduce=None, kv_fp8=False, kv_scale=0.05, own_projections=False, allreduce_norm=None, weight_dtype="bf16"):
-        """allreduce(ptr, count): in-place sum of a [batch, hidden] bf16 tensor over the tensor-parallel ranks, enqueued on
+                 allreduce=None, kv_fp8=False, kv_scale=0.05, own_projections=False, allreduce_norm=None, weight_dtype="bf16", sampling=None):
+        """sampling: None = greedy selection by atoma_argmax_rows (the step as it always was); a dict(history_stride=int, eos_ids=[...]) = the step
+        ends in atoma_sample_batch(append=1) over device buffers the step owns (per-row atoma_sampling_params, uniforms, token history, stop
+        flags; set_sampling / set_uniforms upload them, also between replays of a captured graph) and copies next_ids to ids on the device, so
+        the next step's embedding reads the chosen tokens without a host round trip.
+        allreduce(ptr, count): in-place sum of a [batch, hidden] bf16 tensor over the tensor-parallel ranks, enqueued on
         `stream` -- called after the o and the down projection when `cfg` / `weights` are ONE rank's shard
         (llama_nccl.rs:139,195 via TensorParallelRowLinear, multi_gpu.rs:48-50); None = not tensor parallel."""
         c = self.cfg = cfg
@@ -108,6 +112,22 @@ class DecodeStep:
         self.next_val = ah.DeviceBuffer.zeros((B,), np.float32)
         self.trace = []                                    # (op name, layer, dict of buffers) when keep_intermediates
         self._bufs = {}
+        self.sampling = sampling is not None
+        if self.sampling:
+            self.history_stride = int(sampling.get("history_stride", 4096))
+            eos = np.asarray(list(sampling.get("eos_ids", ())), np.int32)
+            if len(eos) > 16:
+                raise ValueError("DecodeStep(sampling=...): at most 16 eos_ids")
+            self.num_eos = len(eos)
+            self.eos = ah.DeviceBuffer.from_numpy(eos if len(eos) else np.zeros(1, np.int32))
+            self.params = ah.DeviceBuffer.zeros((B,), ah.SAMPLING_PARAMS_DTYPE)      # all zero + penalty 1 below: greedy rows
+            self.u = ah.DeviceBuffer.zeros((B,), np.float32)
+            self.history = ah.DeviceBuffer.zeros((B, self.history_stride), np.int32)
+            self.history_len = ah.DeviceBuffer.zeros((B,), np.int32)
+            self.stop = ah.DeviceBuffer.zeros((B,), np.uint8)
+            greedy = np.zeros(B, ah.SAMPLING_PARAMS_DTYPE)
+            greedy["temperature"], greedy["top_p"], greedy["repetition_penalty"] = 1.0, 1.0, 1.0
+            self.params.upload(greedy)
 
     def _buf(self, name, layer, nbytes):
         key = (name, layer if self.keep else 0)
@@ -124,6 +144,28 @@ class DecodeStep:
         block_table = np.asarray(block_table, np.int32)
         bt[:, :block_table.shape[1]] = block_table
         self.bt.upload(bt)
+
+    def set_sampling(self, params=None, u=None, history=None, history_len=None):
+        """params: array of atoma_hip.SAMPLING_PARAMS_DTYPE [batch]; u: f32 [batch] in [0, 1); history: int32 [batch, <= history_stride] with
+        history_len [batch] valid tokens per row.  Whatever is None keeps its device contents."""
+        assert self.sampling, "DecodeStep was built without sampling="
+        if params is not None:
+            params = np.asarray(params, ah.SAMPLING_PARAMS_DTYPE)
+            assert params.shape == (self.B,)
+            self.params.upload(params)
+        if u is not None:
+            self.set_uniforms(u)
+        if history is not None:
+            history = np.asarray(history, np.int32)
+            h = np.zeros((self.B, self.history_stride), np.int32)
+            h[:, : history.shape[1]] = history
+            self.history.upload(h)
+            self.history_len.upload(np.asarray(history_len, np.int32))
+
+    def set_uniforms(self, u):
+        u = np.asarray(u, np.float32)
+        assert u.shape == (self.B,)
+        self.u.upload(u)
 
     def bind_metadata(self, ids, positions, slots, seqlens, block_table, max_blocks):
         """Use tensors that live elsewhere on the device (raw pointers), e.g. the packed buffer atoma_prepare_inputs uploads."""
@@ -256,7 +298,13 @@ class DecodeStep:
         if not self.fuse_norm:
             self._ok(L.atoma_rms_norm(x.ptr, self.w["norm_f"].ptr, xf.ptr, B, H, H, H, c.eps, BF16, s), "rms_norm")
         self._ok(self.linear(xf.ptr, self.w["lm_head"].ptr, self.logits.ptr, B, H, c.vocab, H, H, c.vocab, BF16, s), "lm_head")
-        self._ok(L.atoma_argmax_rows(self.logits.ptr, B, c.vocab, c.vocab, BF16, self.next_ids.ptr, self.next_val.ptr, s), "argmax")
+        if self.sampling:
+            self._ok(L.atoma_sample_batch(self.logits.ptr, B, c.vocab, c.vocab, BF16, self.params.ptr, self.u.ptr, self.history.ptr, self.history_stride,
+                                          self.history_len.ptr, 1, self.eos.ptr if self.num_eos else None, self.num_eos, self.next_ids.ptr,
+                                          self.next_val.ptr, self.stop.ptr, s), "sample_batch")
+            ah.hip_check(ah.hip.hipMemcpyAsync(self.ids.ptr, self.next_ids.ptr, B * 4, 3, s), "next_ids -> ids")   # the next step's embedding input
+        else:
+            self._ok(L.atoma_argmax_rows(self.logits.ptr, B, c.vocab, c.vocab, BF16, self.next_ids.ptr, self.next_val.ptr, s), "argmax")
         if self.keep:
             self.trace.append(("head", 0, dict(x=x, xf=xf, logits=self.logits)))
 
