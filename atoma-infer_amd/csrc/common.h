@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string>
 #include <vector>
 
@@ -27,6 +28,8 @@ inline bool check_hip(hipError_t e, const char *what) {
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 int device_num_cus();  // CUs of the current device (cached per device)
+
+inline int env_int(const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; }   // an integer knob of the environment
 
 // ---- device-side 16-bit float helpers --------------------------------------------------
 struct bf16_t {};  // tags: storage is always uint16_t bit patterns
@@ -70,6 +73,9 @@ template <typename T> __device__ __forceinline__ float round_through(float f) {
 }
 template <> __device__ __forceinline__ float round_through<bf16_t>(float f) {
     return __uint_as_float(__builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2_v{f, 0.f}, bf16x2_v)) << 16);
+}
+template <typename T> __device__ __forceinline__ float silu_round(float g) {   // silu in f32, rounded to the storage dtype
+    return round_through<T>(g / (1.f + __expf(-g)));
 }
 
 // acc += a.lo*b.lo + a.hi*b.hi on packed 16-bit pairs: v_dot2c_f32_bf16 / v_dot2c_f32_f16

@@ -30,11 +30,8 @@ template <typename T> __global__ void __launch_bounds__(256) add_kernel(const eu
     out[i] = eu32x4{add2<T>(x[0], y[0]), add2<T>(x[1], y[1]), add2<T>(x[2], y[2]), add2<T>(x[3], y[3])};
 }
 
-template <typename T> __device__ __forceinline__ float silu_rounded(float g) {   // silu in f32, rounded to the storage dtype
-    return round_through<T>(g / (1.f + __expf(-g)));
-}
 template <typename T> __device__ __forceinline__ uint32_t silu_mul2(uint32_t g, uint32_t u) {
-    return pack2<T>(silu_rounded<T>(lo_to_f32<T>(g)) * lo_to_f32<T>(u), silu_rounded<T>(hi_to_f32<T>(g)) * hi_to_f32<T>(u));
+    return pack2<T>(silu_round<T>(lo_to_f32<T>(g)) * lo_to_f32<T>(u), silu_round<T>(hi_to_f32<T>(g)) * hi_to_f32<T>(u));
 }
 // gate and up are rows of (possibly the same) wider tensors: row strides in 16-byte chunks
 template <typename T> __global__ void __launch_bounds__(256)

@@ -13,14 +13,14 @@
 // Batches of 1..4 rows (the ones atoma_linear sends here) run linear_gemv_kernel below: loads of 256 contiguous bytes per row and
 // v_dot2c instead of the MFMA operand layout, one launch; 5..16 rows run linear_wg_kernel<RELAY> (the same loads, re-laid into
 // the MFMA operand order through LDS, one launch); the two-launch MFMA-layout kernel at the top serves 17..64 rows.
+// What these kernels share with each other and with the fp8-weight kernels is defined once: the software pipeline, the 16-lane row sum
+// and the kernel that adds K splits in linear_stream.h; the K-split plan, the wavefronts per workgroup, their
+// dispatch and the argument checks in linear_plan.h.
 // Parity: unpinned (Candle / cuBLAS are not in the tree); the oracle is the f64-accumulated product rounded once,
 // the kernel differs from it by at most one unit in the last place (accumulation order).
-#include "common.h"
 #include "norm_shared.h"
-#include "linear_params.h"
-#include <algorithm>
+#include "linear_plan.h"
 #include <stdlib.h>
-#include <type_traits>
 
 namespace atoma {
 
@@ -75,31 +75,7 @@ __global__ void __launch_bounds__(64) linear_decode_kernel(const LinearParams p)
 #pragma unroll
                 for (int c = 0; c < CT; ++c) acc[r][c] = lin_mfma<T>(wb[s][r][q], xb[s][c][q], acc[r][c]);
     };
-    // software pipeline: P chunks in flight; unconditional loads in the steady state keep the vmcnt waits exact
-    int c = c0;
-    if (c0 + 2 * P <= c1) {
-#pragma unroll
-        for (int s = 0; s < P; ++s) issue(s, c0 + s);
-        for (; c + 2 * P <= c1; c += P) {
-#pragma unroll
-            for (int s = 0; s < P; ++s) {
-                compute(s);
-                issue(s, c + s + P);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int s = 0; s < P; ++s)
-            if (c0 + s < c1) issue(s, c0 + s);
-    }
-    for (; c < c1; c += P) {
-#pragma unroll
-        for (int s = 0; s < P; ++s)
-            if (c + s < c1) {
-                compute(s);
-                if (c + s + P < c1) issue(s, c + s + P);
-            }
-    }
+    ATOMA_STREAM_PIPELINE(P, c0, c1, issue, compute, stream_no_op);
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
         if (!has_x[ct]) continue;
@@ -118,37 +94,6 @@ __global__ void __launch_bounds__(64) linear_decode_kernel(const LinearParams p)
             }
         }
     }
-}
-
-// y[b][n] = round(sum over splits of the fp32 partials); 4 outputs per thread.  The epilogues keep the reference's
-// rounding points: the projection's output is rounded to the storage dtype first, then the next op is applied and rounds again.
-template <typename T> __device__ __forceinline__ float4 linear_sum_splits(const LinearParams &p, int64_t i, int64_t total) {
-    float4 a = *reinterpret_cast<const float4 *>(p.partial + i);
-    for (int s = 1; s < p.splits; ++s) {
-        const float4 b = *reinterpret_cast<const float4 *>(p.partial + (int64_t)s * total + i);
-        a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
-    }
-    return make_float4(round_through<T>(a.x), round_through<T>(a.y), round_through<T>(a.z), round_through<T>(a.w));
-}
-template <typename T> __global__ void __launch_bounds__(256) linear_reduce_kernel(const LinearParams p) {
-    const int64_t total = (int64_t)p.batch * p.n;
-    const int out_n = p.epilogue == 2 ? p.n / 2 : p.n;
-    const int64_t o = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;      // index into the [batch, out_n] result
-    if (o >= (int64_t)p.batch * out_n) return;
-    const int64_t row = o / out_n, n = o - row * out_n;
-    float4 a = linear_sum_splits<T>(p, row * p.n + n, total);
-    if (p.epilogue == 1) {
-        const uint2 r = *reinterpret_cast<const uint2 *>(p.aux + row * p.aux_row_stride + n);
-        a.x += lo_to_f32<T>(r.x); a.y += hi_to_f32<T>(r.x); a.z += lo_to_f32<T>(r.y); a.w += hi_to_f32<T>(r.y);
-    } else if (p.epilogue == 2) {
-        const float4 u = linear_sum_splits<T>(p, row * p.n + out_n + n, total);
-        auto silu = [](float g) { return round_through<T>(g / (1.f + __expf(-g))); };
-        a.x = silu(a.x) * u.x; a.y = silu(a.y) * u.y; a.z = silu(a.z) * u.z; a.w = silu(a.w) * u.w;
-    }
-    uint2 w;
-    w.x = pack2<T>(a.x, a.y);
-    w.y = pack2<T>(a.z, a.w);
-    *reinterpret_cast<uint2 *>(p.y + row * p.y_row_stride + n) = w;
 }
 
 // Batches of 1..4 rows, one launch: a workgroup of NW wavefronts owns 16 output features (PAIR: 16 gate + the 16 matching
@@ -227,30 +172,7 @@ __global__ void __launch_bounds__(64 * NW) linear_wg_kernel(const LinearParams p
                 for (int r = 0; r < RT; ++r) acc[r] = lin_mfma<T>(wb[s][r][q], xb[s][q], acc[r]);
         }
     };
-    int c = c0;
-    if (c0 + 2 * P <= c1) {
-#pragma unroll
-        for (int s = 0; s < P; ++s) issue(s, c0 + s);
-        for (; c + 2 * P <= c1; c += P) {
-#pragma unroll
-            for (int s = 0; s < P; ++s) {
-                compute(s);
-                issue(s, c + s + P);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int s = 0; s < P; ++s)
-            if (c0 + s < c1) issue(s, c0 + s);
-    }
-    for (; c < c1; c += P) {
-#pragma unroll
-        for (int s = 0; s < P; ++s)
-            if (c + s < c1) {
-                compute(s);
-                if (c + s + P < c1) issue(s, c + s + P);
-            }
-    }
+    ATOMA_STREAM_PIPELINE(P, c0, c1, issue, compute, stream_no_op);
     // add the NW accumulator tiles: wavefronts 1.. write, wavefront 0 sums (fixed order: deterministic)
     if constexpr (NW > 1) {
         if (wave > 0) {
@@ -279,7 +201,7 @@ __global__ void __launch_bounds__(64 * NW) linear_wg_kernel(const LinearParams p
     }
     if constexpr (PAIR) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = round_through<T>(v[i] / (1.f + __expf(-v[i]))) * round_through<T>(acc[1][i]);
+        for (int i = 0; i < 4; ++i) v[i] = silu_round<T>(v[i]) * round_through<T>(acc[1][i]);
     }
     uint2 o;
     o.x = pack2<T>(v[0], v[1]);
@@ -426,7 +348,7 @@ __global__ void __launch_bounds__(256, 2) linear_mid_kernel(const LinearParams p
             }
             if constexpr (PAIR) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] = round_through<T>(v[i] / (1.f + __expf(-v[i]))) * round_through<T>(acc[1][c][i]);
+                for (int i = 0; i < 4; ++i) v[i] = silu_round<T>(v[i]) * round_through<T>(acc[1][c][i]);
             }
             uint2 o;
             o.x = pack2<T>(v[0], v[1]);
@@ -602,7 +524,7 @@ __global__ void __launch_bounds__(256, 1) linear_big_kernel(const LinearParams p
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const float g = round_through<T>(acc[0][b][4 * j + i]);
-                    v[i] = round_through<T>(g / (1.f + __expf(-g))) * round_through<T>(acc[1][b][4 * j + i]);
+                    v[i] = silu_round<T>(g) * round_through<T>(acc[1][b][4 * j + i]);
                 }
                 uint2 o;
                 o.x = pack2<T>(v[0], v[1]);
@@ -636,13 +558,6 @@ __global__ void __launch_bounds__(256, 1) linear_big_kernel(const LinearParams p
 // 128-input slab) of row 4.rg + g, multiplies them with the matching 8 inputs of every batch row (v_dot2c, fp32) and the 16
 // lanes of a row are summed once at the end (DPP).  Workgroup structure, split of K over NW wavefronts, LDS merge and the
 // epilogues are those of linear_wg_kernel.
-__device__ __forceinline__ float lin_row16_sum(float x) {   // sum over the 16 lanes of a DPP row
-    x += __builtin_amdgcn_update_dpp(0.f, x, 0xB1, 0xf, 0xf, true);    // quad_perm [1,0,3,2]
-    x += __builtin_amdgcn_update_dpp(0.f, x, 0x4E, 0xf, 0xf, true);    // quad_perm [2,3,0,1]
-    x += __builtin_amdgcn_update_dpp(0.f, x, 0x141, 0xf, 0xf, true);   // row_half_mirror
-    x += __builtin_amdgcn_update_dpp(0.f, x, 0x140, 0xf, 0xf, true);   // row_mirror
-    return x;
-}
 // NORM: y = rms_norm(x; norm_w, eps) . W^T -- the RMSNorm in front of the q/k/v and the gate/up projections (llama.rs:402,408)
 // folded into the projection: every wavefront derives the row's scale itself, with the norm kernel's own arithmetic
 // (norm_shared.h: the lane plays the four wavefronts of that kernel's workgroup in turn; 8 KiB of x per batch row from L2, while
@@ -714,32 +629,7 @@ __global__ void __launch_bounds__(64 * NW) linear_gemv_kernel(const LinearParams
     auto scales = [&]() {
         if constexpr (NORM) norm_scales_by_one_wave<T, NB>(p.x, p.x_row_stride, p.batch, p.k, p.norm_eps, lane, nscale);
     };
-    int ch = c0;
-    if (c0 + 2 * P <= c1) {
-#pragma unroll
-        for (int s = 0; s < P; ++s) issue(s, c0 + s);
-        scales();
-        for (; ch + 2 * P <= c1; ch += P) {
-#pragma unroll
-            for (int s = 0; s < P; ++s) {
-                compute(s);
-                issue(s, ch + s + P);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int s = 0; s < P; ++s)
-            if (c0 + s < c1) issue(s, c0 + s);
-        scales();
-    }
-    for (; ch < c1; ch += P) {
-#pragma unroll
-        for (int s = 0; s < P; ++s)
-            if (ch + s < c1) {
-                compute(s);
-                if (ch + s + P < c1) issue(s, ch + s + P);
-            }
-    }
+    ATOMA_STREAM_PIPELINE(P, c0, c1, issue, compute, scales);
     // sum the 16 lanes of every row; lane c == 0 of group g then holds row 4.rg + g
 #pragma unroll
     for (int r = 0; r < RT; ++r)
@@ -747,7 +637,7 @@ __global__ void __launch_bounds__(64 * NW) linear_gemv_kernel(const LinearParams
         for (int rg = 0; rg < 4; ++rg)
 #pragma unroll
             for (int b = 0; b < NB; ++b) {
-                const float v = lin_row16_sum(acc[r][rg][b]);
+                const float v = row16_sum(acc[r][rg][b]);
                 if (c == 0) red[wave][r][rg * 4 + g][b] = v;
             }
     __syncthreads();
@@ -764,151 +654,111 @@ __global__ void __launch_bounds__(64 * NW) linear_gemv_kernel(const LinearParams
         }
         float out = v[0];
         if (p.epilogue == 1) out += lo_to_f32<T>((uint32_t)p.aux[(int64_t)b * p.aux_row_stride + n]);
-        if constexpr (PAIR) out = round_through<T>(out / (1.f + __expf(-out))) * v[1];
+        if constexpr (PAIR) out = silu_round<T>(out) * v[1];
         p.y[(int64_t)b * p.y_row_stride + n] = (uint16_t)f32_to_bits<T>(out);
     }
 }
 
 constexpr int LINEAR_NORM_MAX_BATCH = 2;
-static const int linear_gemv = getenv("ATOMA_LINEAR_GEMV") ? atoi(getenv("ATOMA_LINEAR_GEMV")) : 1;
+static const int linear_gemv = env_int("ATOMA_LINEAR_GEMV", 1);
 // Measured inside the 8B decode step: the VALU kernel wins at ONE row (3.33 against 3.49 ms); from 2 rows up the workgroup kernel
 // with the matrix cores is faster (batch 2: 3.75 -> 3.64 ms, 3: 3.85 -> 3.79, 4: 4.00 -> 3.92), although the single-kernel benchmark
 // still favoured this one up to 4 rows.
-static const int linear_gemv_max_batch = getenv("ATOMA_LINEAR_GEMV_MAX_BATCH") ? atoi(getenv("ATOMA_LINEAR_GEMV_MAX_BATCH")) : 1;
+static const int linear_gemv_max_batch = env_int("ATOMA_LINEAR_GEMV_MAX_BATCH", 1);
 template <typename T> static int launch_linear_gemv(LinearParams &p, hipStream_t stream) {
-    static const int gemv_wpc = getenv("ATOMA_LINEAR_GEMV_WAVES_PER_CU") ? atoi(getenv("ATOMA_LINEAR_GEMV_WAVES_PER_CU")) : 32;
-    const bool pair = p.epilogue == 2;
-    const int64_t tiles = (pair ? p.n / 2 : p.n) / 16, chunks = p.k / 128;
-    // wavefronts per workgroup (the K split inside it) from the W ROWS, not from the workgroups: the stacked gate / up launch then
-    // splits K exactly like the plain projection of the same matrix and stays bit-identical to projection + atoma_silu_mul
-    const int64_t row_tiles = p.n / 16;
-    int nw = 1;
-    while (nw < 8 && row_tiles * nw * 2 <= (int64_t)device_num_cus() * gemv_wpc && chunks / (nw * 2) >= 4) nw *= 2;
+    static const int gemv_wpc = env_int("ATOMA_LINEAR_GEMV_WAVES_PER_CU", 32);
+    const bool pair = p.epilogue == 2, norm = p.norm_w != nullptr;
+    const int64_t tiles = (pair ? p.n / 2 : p.n) / 16;
+    const int nw = waves_per_workgroup(p.n / 16, p.k / 128, gemv_wpc);
     const dim3 grid((unsigned)tiles), block(64 * nw);
-    const bool norm = p.norm_w != nullptr;
-#define ATOMA_GV3(NW_, NB_) do { if (pair) hipLaunchKernelGGL((linear_gemv_kernel<T, NW_, true, NB_, 2>), grid, block, 0, stream, p); \
-                                 else hipLaunchKernelGGL((linear_gemv_kernel<T, NW_, false, NB_, (NB_ > 4 ? 2 : 3)>), grid, block, 0, stream, p); } while (0)
-#define ATOMA_GV3N(NW_, NB_) do { if (!norm) ATOMA_GV3(NW_, NB_); \
-                                  else if (pair) hipLaunchKernelGGL((linear_gemv_kernel<T, NW_, true, NB_, 2, true>), grid, block, 0, stream, p); \
-                                  else hipLaunchKernelGGL((linear_gemv_kernel<T, NW_, false, NB_, 3, true>), grid, block, 0, stream, p); } while (0)
-#define ATOMA_GV2(NW_) do { if (p.batch == 1) ATOMA_GV3N(NW_, 1); else if (p.batch == 2) ATOMA_GV3N(NW_, 2); else if (p.batch <= 4) ATOMA_GV3(NW_, 4); else ATOMA_GV3(NW_, 8); } while (0)
-    switch (nw) {
-        case 1: ATOMA_GV2(1); break;
-        case 2: ATOMA_GV2(2); break;
-        case 4: ATOMA_GV2(4); break;
-        default: ATOMA_GV2(8); break;
-    }
-#undef ATOMA_GV2
-#undef ATOMA_GV3N
-#undef ATOMA_GV3
+    dispatch_nw(nw, [&](auto NW_) {
+        constexpr int NW = decltype(NW_)::value;
+        auto rows = [&](auto NB_) {
+            constexpr int NB = decltype(NB_)::value;
+            if constexpr (NB <= LINEAR_NORM_MAX_BATCH) {
+                if (norm) {
+                    if (pair) hipLaunchKernelGGL((linear_gemv_kernel<T, NW, true, NB, 2, true>), grid, block, 0, stream, p);
+                    else hipLaunchKernelGGL((linear_gemv_kernel<T, NW, false, NB, 3, true>), grid, block, 0, stream, p);
+                    return;
+                }
+            }
+            if (pair) hipLaunchKernelGGL((linear_gemv_kernel<T, NW, true, NB, 2>), grid, block, 0, stream, p);
+            else hipLaunchKernelGGL((linear_gemv_kernel<T, NW, false, NB, (NB > 4 ? 2 : 3)>), grid, block, 0, stream, p);
+        };
+        if (p.batch == 1) rows(int_c<1>{}); else if (p.batch == 2) rows(int_c<2>{}); else if (p.batch <= 4) rows(int_c<4>{}); else rows(int_c<8>{});
+    });
     return ATOMA_CHECK_LAUNCH("linear_gemv_kernel") ? 0 : -1;
 }
 
-static const int linear_wg = getenv("ATOMA_LINEAR_WG") ? atoi(getenv("ATOMA_LINEAR_WG")) : 1;
-static const int linear_wg_max_batch = getenv("ATOMA_LINEAR_WG_MAX_BATCH") ? atoi(getenv("ATOMA_LINEAR_WG_MAX_BATCH")) : 16;
-// wavefronts per workgroup: as many as keep ~8 wavefronts per CU streaming, each with at least 4 chunks (512 inputs)
+static const int linear_wg = env_int("ATOMA_LINEAR_WG", 1);
+static const int linear_wg_max_batch = env_int("ATOMA_LINEAR_WG_MAX_BATCH", 16);
 template <typename T> static int launch_linear_wg(LinearParams &p, hipStream_t stream) {
     const bool pair = p.epilogue == 2;
-    const int64_t tiles = (pair ? p.n / 2 : p.n) / 16, chunks = p.k / 128, row_tiles = p.n / 16;   // nw from the W rows: see launch_linear_gemv
-    int nw = 1;
+    const int64_t tiles = (pair ? p.n / 2 : p.n) / 16;
     // Measured in the whole 8B step (5..16 rows): 4 wavefronts per workgroup for q/k/v, o and down, ONE for gate/up beats the
     // earlier 4 / 8 / 8 / 2 by 7-10 % (fewer, longer streams per CU; the LDS merge of 8 partial sums is not free).
-    static const int wg_wpc = getenv("ATOMA_LINEAR_WG_WAVES_PER_CU") ? atoi(getenv("ATOMA_LINEAR_WG_WAVES_PER_CU")) : 6;
-    while (nw < 8 && row_tiles * nw * 2 <= (int64_t)device_num_cus() * wg_wpc && chunks / (nw * 2) >= 4) nw *= 2;
-    static const int relay_on = getenv("ATOMA_LINEAR_RELAY") ? atoi(getenv("ATOMA_LINEAR_RELAY")) : 1;
-    if (!relay_on && nw == 1 && p.epilogue == 0) return 1;   // MFMA-layout loads: the split-free path visits 512 bytes per row and is 3-5 % faster
+    static const int wg_wpc = env_int("ATOMA_LINEAR_WG_WAVES_PER_CU", 6);
+    const int nw = waves_per_workgroup(p.n / 16, p.k / 128, wg_wpc);
+    static const int relay = env_int("ATOMA_LINEAR_RELAY", 1);
+    if (!relay && nw == 1 && p.epilogue == 0) return 1;   // MFMA-layout loads: the split-free path visits 512 bytes per row and is 3-5 % faster
     const dim3 grid((unsigned)tiles), block(64 * nw);
-    static const int relay = getenv("ATOMA_LINEAR_RELAY") ? atoi(getenv("ATOMA_LINEAR_RELAY")) : 1;
-#define ATOMA_LWG(NW_) do { if (relay) { if (pair) hipLaunchKernelGGL((linear_wg_kernel<T, NW_, true, 2, true>), grid, block, 0, stream, p); \
-                                         else hipLaunchKernelGGL((linear_wg_kernel<T, NW_, false, 3, true>), grid, block, 0, stream, p); } \
-                            else { if (pair) hipLaunchKernelGGL((linear_wg_kernel<T, NW_, true, 2>), grid, block, 0, stream, p); \
-                                   else hipLaunchKernelGGL((linear_wg_kernel<T, NW_, false, 3>), grid, block, 0, stream, p); } } while (0)
-    switch (nw) {
-        case 1: ATOMA_LWG(1); break;
-        case 2: ATOMA_LWG(2); break;
-        case 4: ATOMA_LWG(4); break;
-        default: ATOMA_LWG(8); break;
-    }
-#undef ATOMA_LWG
+    dispatch_nw(nw, [&](auto NW_) {
+        constexpr int NW = decltype(NW_)::value;
+        if (relay) {
+            if (pair) hipLaunchKernelGGL((linear_wg_kernel<T, NW, true, 2, true>), grid, block, 0, stream, p);
+            else hipLaunchKernelGGL((linear_wg_kernel<T, NW, false, 3, true>), grid, block, 0, stream, p);
+        } else {
+            if (pair) hipLaunchKernelGGL((linear_wg_kernel<T, NW, true, 2>), grid, block, 0, stream, p);
+            else hipLaunchKernelGGL((linear_wg_kernel<T, NW, false, 3>), grid, block, 0, stream, p);
+        }
+    });
     return ATOMA_CHECK_LAUNCH("linear_wg_kernel") ? 0 : -1;
 }
 
 // 17..64 rows: linear_mid_kernel (x staged through LDS once per workgroup).  Needs 64 output features per workgroup.
-static const int linear_mid = getenv("ATOMA_LINEAR_MID") ? atoi(getenv("ATOMA_LINEAR_MID")) : 1;
+static const int linear_mid = env_int("ATOMA_LINEAR_MID", 1);
 // measured in the whole step: ONE round of workgroups beats two (fewer partials to merge), no split at all loses
 static const float linear_mid_wg_per_cu = getenv("ATOMA_LINEAR_MID_WG_PER_CU") ? (float)atof(getenv("ATOMA_LINEAR_MID_WG_PER_CU")) : 1.f;
 template <typename T> static int launch_linear_mid(LinearParams &p, hipStream_t stream) {
     const bool pair = p.epilogue == 2;
     const int out_n = pair ? p.n / 2 : p.n;
     if (out_n % 64) return 1;                                  // not served: the caller falls through to linear_decode_kernel
-    const int64_t tiles_n = out_n / 64, chunks = p.k / 128;
     const int ct = (p.batch + 15) / 16;
-    // Split K so that the workgroups fill one round of the CUs (linear_mid_wg_per_cu per CU): the largest split count whose
-    // workgroups still fit one round, never below 4 chunks (512 inputs) per split.  The count is derived from the W ROWS
-    // (p.n / 64), not from the workgroups, so that the stacked gate / up launch with its SiLU.up epilogue splits K exactly like
-    // the plain projection of the same matrix and stays bit-identical to projection + atoma_silu_mul.
-    const int64_t target = (int64_t)((float)device_num_cus() * linear_mid_wg_per_cu), row_tiles = p.n / 64;
-    int64_t splits = std::max<int64_t>(1, std::min<int64_t>(target / std::max<int64_t>(row_tiles, 1), chunks / 4));
-    p.chunks_per_split = (int)cdiv(chunks, splits);
-    p.splits = (int)cdiv(chunks, p.chunks_per_split);
-    p.partial = nullptr;
-    if (p.splits > 1) {
-        p.partial = static_cast<float *>(workspace(stream, (size_t)p.splits * p.batch * p.n * sizeof(float)));
-        if (!p.partial) return -1;
-    }
-    const dim3 grid((unsigned)(tiles_n * p.splits)), block(256);
-#define ATOMA_MID(CT_) do { if (pair) hipLaunchKernelGGL((linear_mid_kernel<T, CT_, true>), grid, block, 0, stream, p); \
-                            else hipLaunchKernelGGL((linear_mid_kernel<T, CT_, false>), grid, block, 0, stream, p); } while (0)
-    switch (ct) {
-        case 1: ATOMA_MID(1); break;
-        case 2: ATOMA_MID(2); break;
-        case 3: ATOMA_MID(3); break;
-        default: ATOMA_MID(4); break;
-    }
-#undef ATOMA_MID
+    // K split so that the workgroups fill one round of the CUs (linear_mid_wg_per_cu per CU)
+    if (!plan_k_splits(p, p.n / 64, (int64_t)((float)device_num_cus() * linear_mid_wg_per_cu), 4, stream, false)) return -1;
+    const dim3 grid((unsigned)(out_n / 64 * p.splits)), block(256);
+    auto launch = [&](auto CT_) {
+        constexpr int CT = decltype(CT_)::value;
+        if (pair) hipLaunchKernelGGL((linear_mid_kernel<T, CT, true>), grid, block, 0, stream, p);
+        else hipLaunchKernelGGL((linear_mid_kernel<T, CT, false>), grid, block, 0, stream, p);
+    };
+    if (ct == 1) launch(int_c<1>{}); else if (ct == 2) launch(int_c<2>{}); else if (ct == 3) launch(int_c<3>{}); else launch(int_c<4>{});
     if (!ATOMA_CHECK_LAUNCH("linear_mid_kernel")) return -1;
-    if (p.partial) {
-        hipLaunchKernelGGL((linear_reduce_kernel<T>), dim3((unsigned)cdiv((int64_t)p.batch * out_n, 1024)), dim3(256), 0, stream, p);
-        if (!ATOMA_CHECK_LAUNCH("linear_reduce_kernel")) return -1;
-    }
-    return 0;
+    return !p.partial || launch_reduce<T>(p, stream) ? 0 : -1;
 }
-
 
 // 65..256 rows: linear_big_kernel.  128 weight rows per workgroup (PAIR: 64 gate + 64 up), one workgroup per CU.
 template <typename T> static int launch_linear_big(LinearParams &p, hipStream_t stream) {
     const bool pair = p.epilogue == 2;
     const int out_n = pair ? p.n / 2 : p.n;
     if (p.n % 128 || p.k % 128) return 1;
-    const int64_t row_tiles = p.n / 128, chunks = p.k / 128;
-    // split K (in units of 128 inputs) until the workgroups fill one round of the CUs; derived from the W rows, so that the
-    // stacked gate / up launch with its epilogue splits exactly like the plain projection (bit-identical results)
+    // K split (in units of 128 inputs) until the workgroups fill one round of the CUs
     static const float big_wg_per_cu = getenv("ATOMA_LINEAR_BIG_WG_PER_CU") ? (float)atof(getenv("ATOMA_LINEAR_BIG_WG_PER_CU")) : 1.f;
-    const int64_t target = (int64_t)((float)device_num_cus() * big_wg_per_cu);
-    int64_t splits = std::max<int64_t>(1, std::min<int64_t>(target / std::max<int64_t>(row_tiles, 1), chunks / 4));
-    p.chunks_per_split = (int)cdiv(chunks, splits);
-    p.splits = (int)cdiv(chunks, p.chunks_per_split);
-    p.partial = nullptr;
-    if (p.splits > 1) {
-        p.partial = static_cast<float *>(workspace(stream, (size_t)p.splits * p.batch * p.n * sizeof(float)));
-        if (!p.partial) return -1;
-    }
+    if (!plan_k_splits(p, p.n / 128, (int64_t)((float)device_num_cus() * big_wg_per_cu), 4, stream, false)) return -1;
     const int64_t tiles_n = pair ? out_n / 64 : out_n / 128;
     const dim3 grid((unsigned)(tiles_n * p.splits)), block(256);
-#define ATOMA_BIG(BM_) do { if (pair) hipLaunchKernelGGL((linear_big_kernel<T, BM_, true>), grid, block, 0, stream, p); \
-                            else hipLaunchKernelGGL((linear_big_kernel<T, BM_, false>), grid, block, 0, stream, p); } while (0)
-    if (p.batch <= 128) ATOMA_BIG(128); else ATOMA_BIG(256);
-#undef ATOMA_BIG
+    auto launch = [&](auto BM_) {
+        constexpr int BM = decltype(BM_)::value;
+        if (pair) hipLaunchKernelGGL((linear_big_kernel<T, BM, true>), grid, block, 0, stream, p);
+        else hipLaunchKernelGGL((linear_big_kernel<T, BM, false>), grid, block, 0, stream, p);
+    };
+    if (p.batch <= 128) launch(int_c<128>{}); else launch(int_c<256>{});
     if (!ATOMA_CHECK_LAUNCH("linear_big_kernel")) return -1;
-    if (p.partial) {
-        hipLaunchKernelGGL((linear_reduce_kernel<T>), dim3((unsigned)cdiv((int64_t)p.batch * out_n, 1024)), dim3(256), 0, stream, p);
-        if (!ATOMA_CHECK_LAUNCH("linear_reduce_kernel")) return -1;
-    }
-    return 0;
+    return !p.partial || launch_reduce<T>(p, stream) ? 0 : -1;
 }
 
 // 512 bytes per weight-row visit (two 128-input chunks per pipeline stage) when the split allows: +2-5 % over 256
-static const int linear_ch = getenv("ATOMA_LINEAR_CH") ? atoi(getenv("ATOMA_LINEAR_CH")) : 2;
+static const int linear_ch = env_int("ATOMA_LINEAR_CH", 2);
 template <typename T> static int launch_linear(LinearParams &p, hipStream_t stream) {
     // the self-normalising variant serves 1 and 2 rows: at 4 rows the normalisation of x (45 VALU instructions per row and 128-input
     // chunk, repeated by every wavefront) makes the kernel VALU-bound -- measured 4.82 ms against 4.06 ms for the 8B step
@@ -940,14 +790,7 @@ template <typename T> static int launch_linear(LinearParams &p, hipStream_t stre
     if (p.batch > 16) {
         int rc = launch_linear_tile(p, std::is_same<T, bf16_t>::value ? ATOMA_BF16 : ATOMA_F16, stream);
         if (rc < 0) return rc;
-        if (rc == 0) {
-            if (p.partial) {
-                const int out_n = p.epilogue == 2 ? p.n / 2 : p.n;
-                hipLaunchKernelGGL((linear_reduce_kernel<T>), dim3((unsigned)cdiv((int64_t)p.batch * out_n, 1024)), dim3(256), 0, stream, p);
-                if (!ATOMA_CHECK_LAUNCH("linear_reduce_kernel")) return -1;
-            }
-            return 0;
-        }
+        if (rc == 0) return !p.partial || launch_reduce<T>(p, stream) ? 0 : -1;
     }
     if (linear_mid && p.batch > 16) {
         const int rc = launch_linear_mid<T>(p, stream);
@@ -958,17 +801,9 @@ template <typename T> static int launch_linear(LinearParams &p, hipStream_t stre
     // row tiles per wave: bounded by the 256 registers of two wavefronts per SIMD (x fragments: 16 registers per column tile and chunk in flight)
     const int rt = ct > 1 ? ((ct < 4 && p.n % 32 == 0) ? 2 : 1) : ((p.batch > 2 && p.n % 64 == 0) ? 4 : 1);
     const int64_t tiles_n = p.n / (16 * rt);
-    // split K until about 8 (one row tile) / 4 (more bytes in flight per wave) wavefronts per CU stream the weights,
-    // never below 4 chunks (512 inputs) per split
-    const int64_t target = (int64_t)device_num_cus() * (rt > 1 ? 4 : 8);
-    int64_t splits = std::max<int64_t>(1, std::min<int64_t>(target / std::max<int64_t>(tiles_n, 1), chunks / 4));
-    p.chunks_per_split = (int)cdiv(chunks, splits);
-    p.splits = (int)cdiv(chunks, p.chunks_per_split);
-    p.partial = nullptr;
-    if (p.splits > 1 || p.epilogue != 0) {   // an epilogue always runs in the reduce kernel (it needs whole rows of y)
-        p.partial = static_cast<float *>(workspace(stream, (size_t)p.splits * p.batch * p.n * sizeof(float)));
-        if (!p.partial) return -1;
-    }
+    // split K until about 8 (one row tile) / 4 (more bytes in flight per wave) wavefronts per CU stream the weights;
+    // an epilogue always runs in the reduce kernel (it needs whole rows of y)
+    if (!plan_k_splits(p, tiles_n, (int64_t)device_num_cus() * (rt > 1 ? 4 : 8), 4, stream, p.epilogue != 0)) return -1;
     const dim3 grid((unsigned)(tiles_n * p.splits));
     const int ch = (rt == 1 && ct == 1 && p.chunks_per_split % 2 == 0 && chunks % 2 == 0) ? linear_ch : 1;
 #define ATOMA_LIN(RT_, CT_, P_, CH_) hipLaunchKernelGGL((linear_decode_kernel<T, RT_, CT_, P_, CH_>), grid, dim3(64), 0, stream, p)
@@ -986,11 +821,7 @@ template <typename T> static int launch_linear(LinearParams &p, hipStream_t stre
     }
 #undef ATOMA_LIN
     if (!ATOMA_CHECK_LAUNCH("linear_decode_kernel")) return -1;
-    if (p.partial) {
-        hipLaunchKernelGGL((linear_reduce_kernel<T>), dim3((unsigned)cdiv((int64_t)p.batch * p.n, 1024)), dim3(256), 0, stream, p);
-        if (!ATOMA_CHECK_LAUNCH("linear_reduce_kernel")) return -1;
-    }
-    return 0;
+    return !p.partial || launch_reduce<T>(p, stream) ? 0 : -1;
 }
 
 }  // namespace atoma
@@ -1008,19 +839,7 @@ static int linear_decode_entry(const void *x, const void *w, void *y, int64_t ba
     if (norm_w && in_features > 8 * 8 * NORM_THREADS) { set_error("linear_decode: the fused RMSNorm supports in_features <= 16384"); return -1; }
     if (dtype != ATOMA_F16 && dtype != ATOMA_BF16) { set_error("linear_decode: dtype must be f16 or bf16"); return -1; }
     if (batch < 0 || batch > 256) { set_error("linear_decode: batch must be in [0, 256]"); return -1; }
-    if (in_features <= 0 || in_features % 128 != 0) { set_error("linear_decode: in_features must be a positive multiple of 128"); return -1; }
-    if (out_features <= 0 || out_features % 16 != 0) { set_error("linear_decode: out_features must be a positive multiple of 16"); return -1; }
-    const int64_t y_width = epilogue == 2 ? out_features / 2 : out_features;
-    if (epilogue < 0 || epilogue > 2) { set_error("linear_decode: unknown epilogue"); return -1; }
-    if (epilogue == 2 && out_features % 32 != 0) { set_error("linear_decode: the silu.up epilogue needs out_features to be a multiple of 32"); return -1; }
-    if (epilogue == 1 && (!aux || aux_row_stride < out_features || aux_row_stride % 4 || (reinterpret_cast<uintptr_t>(aux) & 7u))) {
-        set_error("linear_decode: the residual epilogue needs an 8-byte aligned [batch, out_features] tensor");
-        return -1;
-    }
-    if (x_row_stride < in_features || w_row_stride < in_features || y_row_stride < y_width) {
-        set_error("linear_decode: row strides must cover a row");
-        return -1;
-    }
+    if (!check_linear_args("linear_decode", in_features, out_features, x_row_stride, w_row_stride, y_row_stride, epilogue, aux, aux_row_stride)) return -1;
     if (x_row_stride % 8 || w_row_stride % 8 || y_row_stride % 4) { set_error("linear_decode: strides must keep rows 16-byte (x, w) / 8-byte (y) aligned"); return -1; }
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w)) & 15u || reinterpret_cast<uintptr_t>(y) & 7u) {
         set_error("linear_decode: x and w must be 16-byte aligned, y 8-byte aligned");
@@ -1032,13 +851,7 @@ static int linear_decode_entry(const void *x, const void *w, void *y, int64_t ba
         return -1;
     }
     if (batch == 0) return 0;
-    LinearParams p{};
-    p.x = static_cast<const uint16_t *>(x);
-    p.w = static_cast<const uint16_t *>(w);
-    p.y = static_cast<uint16_t *>(y);
-    p.x_row_stride = x_row_stride; p.w_row_stride = w_row_stride; p.y_row_stride = y_row_stride;
-    p.batch = (int)batch; p.n = (int)out_features; p.k = (int)in_features;
-    p.epilogue = epilogue; p.aux = static_cast<const uint16_t *>(aux); p.aux_row_stride = aux_row_stride;
+    LinearParams p = linear_params_of(x, w, y, batch, in_features, out_features, x_row_stride, w_row_stride, y_row_stride, epilogue, aux, aux_row_stride);
     p.norm_w = static_cast<const uint16_t *>(norm_w); p.norm_eps = norm_eps;
     const auto s = static_cast<hipStream_t>(stream);
     int rc = dtype == ATOMA_BF16 ? launch_linear<bf16_t>(p, s) : launch_linear<f16_t>(p, s);

@@ -11,31 +11,21 @@
 //   * 5..16 rows  linear_fp8w_wg_kernel: the same loads re-laid into the MFMA A-operand order through a 4 KiB LDS tile per wavefront; one
 //                 16-byte LDS read feeds two MFMAs (its low and its high 8 bytes: the k order inside an MFMA is free as long as x agrees);
 //   * 17..64 rows linear_fp8w_mma_kernel: loads in the MFMA operand order, K split over wavefronts into the fp32 workspace, and
-//                 linear_fp8w_reduce_kernel (sum, scale, round, epilogue).
+//                 linear_reduce_kernel<T, SCALED> (sum, scale, round, epilogue).
 // W by non-temporal buffer loads (read once), x from L2.  in_features is a multiple of 128, so the last 256-input slab of the first two kernels
 // may be half a slab: its upper half is not loaded (zeros for W and x).  The split counts derive from the W rows, never from the epilogue, so
 // _residual and _silu_mul are bit-identical to the plain call followed by atoma_add / atoma_silu_mul.
+// Pipeline, row sum and the reduce kernel are those of the 16-bit kernels (linear_stream.h), the parameters are LinearParams with
+// byte weights and w_scale, the launch plans and the shared argument checks are linear_plan.h's.
 // Out of scope here: the fused RMSNorm and q/k/v + RoPE + cache forms, 65..256 rows and prefill-sized products (16-bit weights only).
 // atoma_quantize_weight_fp8 at the bottom: the KV-cache write's arithmetic (kv_fp8.hip) with one scale per output row, amax / 448.
-#include "common.h"
-#include "linear_params.h"
-#include <algorithm>
+#include "linear_plan.h"
 #include <stdlib.h>
 
 namespace atoma {
 
-struct LinearFp8wParams {
-    const uint16_t *x;
-    const uint8_t *w;            // e4m3fn bytes [n][k]
-    const float *w_scale;        // [n]
-    uint16_t *y;
-    float *partial;              // [splits][batch][n] fp32 (unscaled sums), or null
-    int64_t x_row_stride, w_row_stride, y_row_stride;   // x, y in elements; w in bytes
-    int batch, n, k, splits, chunks_per_split;           // chunk = 128 inputs (linear_fp8w_mma_kernel)
-    int epilogue;                // as LinearParams: 0 none; 1 + residual; 2 silu(gate) * up over stacked gate / up rows
-    const uint16_t *aux;
-    int64_t aux_row_stride;
-};
+// LinearParams here: w = e4m3fn bytes [n][k] (w8_bytes), w_row_stride in bytes, w_scale [n], partial = UNSCALED fp32 sums
+__device__ __forceinline__ const uint8_t *w8_bytes(const LinearParams &p) { return reinterpret_cast<const uint8_t *>(p.w); }
 
 // two fp8 bytes of `word` (bytes 0,1 or, hi, bytes 2,3) -> one packed pair of T, exact
 template <typename T> __device__ __forceinline__ uint32_t w8_pair(uint32_t word, bool hi);
@@ -52,19 +42,11 @@ template <typename T> __device__ __forceinline__ lu32x4 w8_frag(uint32_t w0, uin
     return lu32x4{w8_pair<T>(w0, false), w8_pair<T>(w0, true), w8_pair<T>(w1, false), w8_pair<T>(w1, true)};
 }
 
-__device__ __forceinline__ float w8_row16_sum(float x) {   // sum over the 16 lanes of a DPP row (linear_decode.hip: lin_row16_sum)
-    x += __builtin_amdgcn_update_dpp(0.f, x, 0xB1, 0xf, 0xf, true);
-    x += __builtin_amdgcn_update_dpp(0.f, x, 0x4E, 0xf, 0xf, true);
-    x += __builtin_amdgcn_update_dpp(0.f, x, 0x141, 0xf, 0xf, true);
-    x += __builtin_amdgcn_update_dpp(0.f, x, 0x140, 0xf, 0xf, true);
-    return x;
-}
-
 // 1..4 rows.  Workgroup = NW wavefronts x 16 output features (PAIR: + the 16 matching up features); wavefront w streams the w-th part of K
 // in slabs of 256 inputs: lane 16.g + c loads bytes 16c..16c+15 of row 4.rg + g (4 rows x 256 B per instruction), converts them to 8 pairs
 // and multiplies with the matching 16 inputs of every batch row (two 16-byte loads of x).  Merge over LDS and epilogues as linear_gemv_kernel.
 template <typename T, int NW, bool PAIR, int NB, int P>
-__global__ void __launch_bounds__(64 * NW) linear_fp8w_gemv_kernel(const LinearFp8wParams p) {
+__global__ void __launch_bounds__(64 * NW) linear_fp8w_gemv_kernel(const LinearParams p) {
     constexpr int RT = PAIR ? 2 : 1;
     __shared__ float red[NW][RT][16][4];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), g = lane >> 4, c = lane & 15;
@@ -75,7 +57,7 @@ __global__ void __launch_bounds__(64 * NW) linear_fp8w_gemv_kernel(const LinearF
     const int c0 = wave * per, c1 = min(c0 + per, slabs);
     const int64_t row_bytes = p.w_row_stride;
 
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(p.w + (int64_t)n0 * row_bytes), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(w8_bytes(p) + (int64_t)n0 * row_bytes), 0, 0x7fffffff, 0x00020000);
     uint32_t w_lane[RT];
 #pragma unroll
     for (int r = 0; r < RT; ++r) w_lane[r] = (uint32_t)(((int64_t)r * out_n + g) * row_bytes + c * 16);
@@ -120,30 +102,7 @@ __global__ void __launch_bounds__(64 * NW) linear_fp8w_gemv_kernel(const LinearF
                 }
             }
     };
-    int ch = c0;
-    if (c0 + 2 * P <= c1) {
-#pragma unroll
-        for (int s = 0; s < P; ++s) issue(s, c0 + s);
-        for (; ch + 2 * P <= c1; ch += P) {
-#pragma unroll
-            for (int s = 0; s < P; ++s) {
-                compute(s);
-                issue(s, ch + s + P);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int s = 0; s < P; ++s)
-            if (c0 + s < c1) issue(s, c0 + s);
-    }
-    for (; ch < c1; ch += P) {
-#pragma unroll
-        for (int s = 0; s < P; ++s)
-            if (ch + s < c1) {
-                compute(s);
-                if (ch + s + P < c1) issue(s, ch + s + P);
-            }
-    }
+    ATOMA_STREAM_PIPELINE(P, c0, c1, issue, compute, stream_no_op);
     // sum the 16 lanes of every row; lane c == 0 of group g then holds row 4.rg + g
 #pragma unroll
     for (int r = 0; r < RT; ++r)
@@ -151,7 +110,7 @@ __global__ void __launch_bounds__(64 * NW) linear_fp8w_gemv_kernel(const LinearF
         for (int rg = 0; rg < 4; ++rg)
 #pragma unroll
             for (int b = 0; b < NB; ++b) {
-                const float v = w8_row16_sum(acc[r][rg][b]);
+                const float v = row16_sum(acc[r][rg][b]);
                 if (c == 0) red[wave][r][rg * 4 + g][b] = v;
             }
     __syncthreads();
@@ -168,7 +127,7 @@ __global__ void __launch_bounds__(64 * NW) linear_fp8w_gemv_kernel(const LinearF
     }
     float out = v[0];
     if (p.epilogue == 1) out += lo_to_f32<T>((uint32_t)p.aux[(int64_t)b * p.aux_row_stride + n]);
-    if constexpr (PAIR) out = round_through<T>(out / (1.f + __expf(-out))) * v[1];
+    if constexpr (PAIR) out = silu_round<T>(out) * v[1];
     p.y[(int64_t)b * p.y_row_stride + n] = (uint16_t)f32_to_bits<T>(out);
 }
 
@@ -177,7 +136,7 @@ __global__ void __launch_bounds__(64 * NW) linear_fp8w_gemv_kernel(const LinearF
 // [row col][piece (4q + grp) ^ col] = inputs 16.(4q + grp) ..+15 of the slab; the low 8 bytes are the A operand of one MFMA, the high 8 of the
 // next, against x[col][the same inputs].  Result tile: lane holds y^T[n0 + 4.grp + i][batch row col].
 template <typename T, int NW, bool PAIR, int P>
-__global__ void __launch_bounds__(64 * NW) linear_fp8w_wg_kernel(const LinearFp8wParams p) {
+__global__ void __launch_bounds__(64 * NW) linear_fp8w_wg_kernel(const LinearParams p) {
     constexpr int RT = PAIR ? 2 : 1;
     __shared__ float red[NW > 1 ? NW - 1 : 1][RT][64][4];
     __shared__ __attribute__((aligned(16))) char relay[NW][RT][4096];
@@ -189,7 +148,7 @@ __global__ void __launch_bounds__(64 * NW) linear_fp8w_wg_kernel(const LinearFp8
     const int c0 = wave * per, c1 = min(c0 + per, slabs);
     const int64_t row_bytes = p.w_row_stride;
 
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(p.w + (int64_t)n0 * row_bytes), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(w8_bytes(p) + (int64_t)n0 * row_bytes), 0, 0x7fffffff, 0x00020000);
     uint32_t w_lane[RT];
 #pragma unroll
     for (int r = 0; r < RT; ++r) w_lane[r] = (uint32_t)(((int64_t)r * out_n + grp) * row_bytes + col * 16);   // row 4.q + grp, piece col
@@ -240,30 +199,7 @@ __global__ void __launch_bounds__(64 * NW) linear_fp8w_wg_kernel(const LinearFp8
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
     };
-    int c = c0;
-    if (c0 + 2 * P <= c1) {
-#pragma unroll
-        for (int s = 0; s < P; ++s) issue(s, c0 + s);
-        for (; c + 2 * P <= c1; c += P) {
-#pragma unroll
-            for (int s = 0; s < P; ++s) {
-                compute(s);
-                issue(s, c + s + P);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int s = 0; s < P; ++s)
-            if (c0 + s < c1) issue(s, c0 + s);
-    }
-    for (; c < c1; c += P) {
-#pragma unroll
-        for (int s = 0; s < P; ++s)
-            if (c + s < c1) {
-                compute(s);
-                if (c + s + P < c1) issue(s, c + s + P);
-            }
-    }
+    ATOMA_STREAM_PIPELINE(P, c0, c1, issue, compute, stream_no_op);
     // add the NW accumulator tiles: wavefronts 1.. write, wavefront 0 sums (fixed order: deterministic)
     if constexpr (NW > 1) {
         if (wave > 0) {
@@ -291,7 +227,7 @@ __global__ void __launch_bounds__(64 * NW) linear_fp8w_wg_kernel(const LinearFp8
     }
     if constexpr (PAIR) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = round_through<T>(v[i] / (1.f + __expf(-v[i]))) * round_through<T>(acc[1][i] * p.w_scale[(int64_t)out_n + n + i]);
+        for (int i = 0; i < 4; ++i) v[i] = silu_round<T>(v[i]) * round_through<T>(acc[1][i] * p.w_scale[(int64_t)out_n + n + i]);
     }
     uint2 o;
     o.x = pack2<T>(v[0], v[1]);
@@ -302,16 +238,16 @@ __global__ void __launch_bounds__(64 * NW) linear_fp8w_wg_kernel(const LinearFp8
 // 17..64 rows.  One wavefront per (16.RT output features, K split), loads in the MFMA operand order: lane 16.grp + col loads bytes
 // 64q + 16.grp ..+15 of row 16r + col of a 128-input chunk (q = 0, 1) -- two A operands -- and the matching 32 bytes of x rows 16c + col.
 // CT column tiles of 16 batch rows share every converted A operand.  Unscaled fp32 sums go to the workspace [split][batch][n] when K is
-// split or an epilogue follows (linear_fp8w_reduce_kernel); otherwise scaled, rounded and stored here.
+// split or an epilogue follows (linear_reduce_kernel<T, SCALED>); otherwise scaled, rounded and stored here.
 template <typename T, int RT, int CT, int P>
-__global__ void __launch_bounds__(64) linear_fp8w_mma_kernel(const LinearFp8wParams p) {
+__global__ void __launch_bounds__(64) linear_fp8w_mma_kernel(const LinearParams p) {
     const int lane = threadIdx.x, grp = lane >> 4, col = lane & 15;
     const int tiles_n = p.n / (16 * RT);
     const int tile = blockIdx.x % tiles_n, split = blockIdx.x / tiles_n;
     const int n0 = tile * 16 * RT;
     const int c0 = split * p.chunks_per_split, c1 = min(c0 + p.chunks_per_split, p.k >> 7);
 
-    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(p.w + (int64_t)n0 * p.w_row_stride), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wr = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(w8_bytes(p) + (int64_t)n0 * p.w_row_stride), 0, 0x7fffffff, 0x00020000);
     uint32_t w_lane[RT];
 #pragma unroll
     for (int r = 0; r < RT; ++r) w_lane[r] = (uint32_t)((16 * r + col) * p.w_row_stride + grp * 16);
@@ -355,30 +291,7 @@ __global__ void __launch_bounds__(64) linear_fp8w_mma_kernel(const LinearFp8wPar
                 }
             }
     };
-    int c = c0;
-    if (c0 + 2 * P <= c1) {
-#pragma unroll
-        for (int s = 0; s < P; ++s) issue(s, c0 + s);
-        for (; c + 2 * P <= c1; c += P) {
-#pragma unroll
-            for (int s = 0; s < P; ++s) {
-                compute(s);
-                issue(s, c + s + P);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int s = 0; s < P; ++s)
-            if (c0 + s < c1) issue(s, c0 + s);
-    }
-    for (; c < c1; c += P) {
-#pragma unroll
-        for (int s = 0; s < P; ++s)
-            if (c + s < c1) {
-                compute(s);
-                if (c + s + P < c1) issue(s, c + s + P);
-            }
-    }
+    ATOMA_STREAM_PIPELINE(P, c0, c1, issue, compute, stream_no_op);
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
         if (!has_x[ct]) continue;
@@ -399,119 +312,60 @@ __global__ void __launch_bounds__(64) linear_fp8w_mma_kernel(const LinearFp8wPar
     }
 }
 
-// y[b][n] = round(scale[n] * sum over splits of the fp32 partials), then the epilogue with the rounding points of linear_reduce_kernel
-template <typename T> __device__ __forceinline__ float4 linear_fp8w_sum_splits(const LinearFp8wParams &p, int64_t i, int64_t n, int64_t total) {
-    float4 a = *reinterpret_cast<const float4 *>(p.partial + i);
-    for (int s = 1; s < p.splits; ++s) {
-        const float4 b = *reinterpret_cast<const float4 *>(p.partial + (int64_t)s * total + i);
-        a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
-    }
-    const float *sc = p.w_scale + n;
-    return make_float4(round_through<T>(a.x * sc[0]), round_through<T>(a.y * sc[1]), round_through<T>(a.z * sc[2]), round_through<T>(a.w * sc[3]));
-}
-template <typename T> __global__ void __launch_bounds__(256) linear_fp8w_reduce_kernel(const LinearFp8wParams p) {
-    const int64_t total = (int64_t)p.batch * p.n;
-    const int out_n = p.epilogue == 2 ? p.n / 2 : p.n;
-    const int64_t o = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;      // index into the [batch, out_n] result
-    if (o >= (int64_t)p.batch * out_n) return;
-    const int64_t row = o / out_n, n = o - row * out_n;
-    float4 a = linear_fp8w_sum_splits<T>(p, row * p.n + n, n, total);
-    if (p.epilogue == 1) {
-        const uint2 r = *reinterpret_cast<const uint2 *>(p.aux + row * p.aux_row_stride + n);
-        a.x += lo_to_f32<T>(r.x); a.y += hi_to_f32<T>(r.x); a.z += lo_to_f32<T>(r.y); a.w += hi_to_f32<T>(r.y);
-    } else if (p.epilogue == 2) {
-        const float4 u = linear_fp8w_sum_splits<T>(p, row * p.n + out_n + n, out_n + n, total);
-        auto silu = [](float g) { return round_through<T>(g / (1.f + __expf(-g))); };
-        a.x = silu(a.x) * u.x; a.y = silu(a.y) * u.y; a.z = silu(a.z) * u.z; a.w = silu(a.w) * u.w;
-    }
-    uint2 w;
-    w.x = pack2<T>(a.x, a.y);
-    w.y = pack2<T>(a.z, a.w);
-    *reinterpret_cast<uint2 *>(p.y + row * p.y_row_stride + n) = w;
-}
-
 // ---- launchers ---------------------------------------------------------------------------------------------------------------------------
 // Wavefronts per workgroup (the K split inside it) from the W ROWS, as launch_linear_gemv / launch_linear_wg do, so that the stacked gate / up
 // launch splits K exactly like the plain projection of the same matrix.  A slab is 256 inputs = 4 KiB per load round of a wavefront, the same
 // bytes as a 128-input chunk of the 16-bit kernels, so the depth rule carries over in slabs: at least 4 slabs (1024 inputs) per wavefront --
 // half the K split of the 16-bit kernel at the same K, and the same bytes in flight per wavefront (P x 4 KiB per row tile).
-static const int fp8w_gemv_max_batch = getenv("ATOMA_FP8W_GEMV_MAX_BATCH") ? atoi(getenv("ATOMA_FP8W_GEMV_MAX_BATCH")) : 4;
-static const int fp8w_wg_max_batch = getenv("ATOMA_FP8W_WG_MAX_BATCH") ? atoi(getenv("ATOMA_FP8W_WG_MAX_BATCH")) : 16;
-static int fp8w_waves(const LinearFp8wParams &p, int waves_per_cu) {
-    const int64_t row_tiles = p.n / 16, slabs = (p.k + 255) / 256;
-    int nw = 1;
-    while (nw < 8 && row_tiles * nw * 2 <= (int64_t)device_num_cus() * waves_per_cu && slabs / (nw * 2) >= 4) nw *= 2;
-    return nw;
-}
+static const int fp8w_gemv_max_batch = env_int("ATOMA_FP8W_GEMV_MAX_BATCH", 4);
+static const int fp8w_wg_max_batch = env_int("ATOMA_FP8W_WG_MAX_BATCH", 16);
 
-template <typename T> static int launch_fp8w_gemv(LinearFp8wParams &p, hipStream_t stream) {
-    static const int wpc = getenv("ATOMA_FP8W_GEMV_WAVES_PER_CU") ? atoi(getenv("ATOMA_FP8W_GEMV_WAVES_PER_CU")) : 32;
+template <typename T> static int launch_fp8w_gemv(LinearParams &p, hipStream_t stream) {
+    static const int wpc = env_int("ATOMA_FP8W_GEMV_WAVES_PER_CU", 32);
     const bool pair = p.epilogue == 2;
-    const int nw = fp8w_waves(p, wpc);
+    const int nw = waves_per_workgroup(p.n / 16, (p.k + 255) / 256, wpc);
     const dim3 grid((unsigned)((pair ? p.n / 2 : p.n) / 16)), block(64 * nw);
-#define ATOMA_F8GV3(NW_, NB_) do { if (pair) hipLaunchKernelGGL((linear_fp8w_gemv_kernel<T, NW_, true, NB_, (NB_ > 2 ? 1 : 2)>), grid, block, 0, stream, p); \
-                                   else hipLaunchKernelGGL((linear_fp8w_gemv_kernel<T, NW_, false, NB_, (NB_ > 2 ? 2 : 3)>), grid, block, 0, stream, p); } while (0)
-#define ATOMA_F8GV2(NW_) do { if (p.batch == 1) ATOMA_F8GV3(NW_, 1); else if (p.batch == 2) ATOMA_F8GV3(NW_, 2); else ATOMA_F8GV3(NW_, 4); } while (0)
-    switch (nw) {
-        case 1: ATOMA_F8GV2(1); break;
-        case 2: ATOMA_F8GV2(2); break;
-        case 4: ATOMA_F8GV2(4); break;
-        default: ATOMA_F8GV2(8); break;
-    }
-#undef ATOMA_F8GV2
-#undef ATOMA_F8GV3
+    dispatch_nw(nw, [&](auto NW_) {
+        constexpr int NW = decltype(NW_)::value;
+        auto rows = [&](auto NB_) {
+            constexpr int NB = decltype(NB_)::value;
+            if (pair) hipLaunchKernelGGL((linear_fp8w_gemv_kernel<T, NW, true, NB, (NB > 2 ? 1 : 2)>), grid, block, 0, stream, p);
+            else hipLaunchKernelGGL((linear_fp8w_gemv_kernel<T, NW, false, NB, (NB > 2 ? 2 : 3)>), grid, block, 0, stream, p);
+        };
+        if (p.batch == 1) rows(int_c<1>{}); else if (p.batch == 2) rows(int_c<2>{}); else rows(int_c<4>{});
+    });
     return ATOMA_CHECK_LAUNCH("linear_fp8w_gemv_kernel") ? 0 : -1;
 }
 
-template <typename T> static int launch_fp8w_wg(LinearFp8wParams &p, hipStream_t stream) {
-    static const int wpc = getenv("ATOMA_FP8W_WG_WAVES_PER_CU") ? atoi(getenv("ATOMA_FP8W_WG_WAVES_PER_CU")) : 8;
+template <typename T> static int launch_fp8w_wg(LinearParams &p, hipStream_t stream) {
+    static const int wpc = env_int("ATOMA_FP8W_WG_WAVES_PER_CU", 8);
     const bool pair = p.epilogue == 2;
-    const int nw = fp8w_waves(p, wpc);
+    const int nw = waves_per_workgroup(p.n / 16, (p.k + 255) / 256, wpc);
     const dim3 grid((unsigned)((pair ? p.n / 2 : p.n) / 16)), block(64 * nw);
-#define ATOMA_F8WG(NW_) do { if (pair) hipLaunchKernelGGL((linear_fp8w_wg_kernel<T, NW_, true, 2>), grid, block, 0, stream, p); \
-                             else hipLaunchKernelGGL((linear_fp8w_wg_kernel<T, NW_, false, 3>), grid, block, 0, stream, p); } while (0)
-    switch (nw) {
-        case 1: ATOMA_F8WG(1); break;
-        case 2: ATOMA_F8WG(2); break;
-        case 4: ATOMA_F8WG(4); break;
-        default: ATOMA_F8WG(8); break;
-    }
-#undef ATOMA_F8WG
+    dispatch_nw(nw, [&](auto NW_) {
+        constexpr int NW = decltype(NW_)::value;
+        if (pair) hipLaunchKernelGGL((linear_fp8w_wg_kernel<T, NW, true, 2>), grid, block, 0, stream, p);
+        else hipLaunchKernelGGL((linear_fp8w_wg_kernel<T, NW, false, 3>), grid, block, 0, stream, p);
+    });
     return ATOMA_CHECK_LAUNCH("linear_fp8w_wg_kernel") ? 0 : -1;
 }
 
-template <typename T> static int launch_fp8w_mma(LinearFp8wParams &p, hipStream_t stream) {
-    const int64_t chunks = p.k / 128;
+template <typename T> static int launch_fp8w_mma(LinearParams &p, hipStream_t stream) {
     const int ct = (p.batch + 15) / 16;
     const int rt = p.n % 32 == 0 ? 2 : 1;
     const int64_t tiles_n = p.n / (16 * rt);
     // Split K until about 4 (two row tiles) / 8 wavefronts per CU stream the weights, never below 8 chunks per split: 1 KiB per weight row and
-    // split, the bytes the 16-bit kernel's floor of 4 chunks stands for.  From the W rows (p.n): the epilogues split like the plain product.
-    const int64_t target = (int64_t)device_num_cus() * (rt > 1 ? 4 : 8);
-    const int64_t splits = std::max<int64_t>(1, std::min<int64_t>(target / std::max<int64_t>(tiles_n, 1), chunks / 8));
-    p.chunks_per_split = (int)cdiv(chunks, splits);
-    p.splits = (int)cdiv(chunks, p.chunks_per_split);
-    p.partial = nullptr;
-    if (p.splits > 1 || p.epilogue != 0) {   // an epilogue always runs in the reduce kernel (it needs whole rows of y)
-        p.partial = static_cast<float *>(workspace(stream, (size_t)p.splits * p.batch * p.n * sizeof(float)));
-        if (!p.partial) return -1;
-    }
+    // split, the bytes the 16-bit kernel's floor of 4 chunks stands for.  An epilogue always runs in the reduce kernel (it needs whole rows of y).
+    if (!plan_k_splits(p, tiles_n, (int64_t)device_num_cus() * (rt > 1 ? 4 : 8), 8, stream, p.epilogue != 0)) return -1;
     const dim3 grid((unsigned)(tiles_n * p.splits));
-#define ATOMA_F8MMA(RT_, CT_) hipLaunchKernelGGL((linear_fp8w_mma_kernel<T, RT_, CT_, 2>), grid, dim3(64), 0, stream, p)
-#define ATOMA_F8MMA_CT(RT_) do { if (ct <= 1) ATOMA_F8MMA(RT_, 1); else if (ct == 2) ATOMA_F8MMA(RT_, 2); else if (ct == 3) ATOMA_F8MMA(RT_, 3); else ATOMA_F8MMA(RT_, 4); } while (0)
-    if (rt == 2) ATOMA_F8MMA_CT(2); else ATOMA_F8MMA_CT(1);
-#undef ATOMA_F8MMA_CT
-#undef ATOMA_F8MMA
+    auto launch = [&](auto RT_, auto CT_) { hipLaunchKernelGGL((linear_fp8w_mma_kernel<T, decltype(RT_)::value, decltype(CT_)::value, 2>), grid, dim3(64), 0, stream, p); };
+    auto cols = [&](auto RT_) { if (ct <= 1) launch(RT_, int_c<1>{}); else if (ct == 2) launch(RT_, int_c<2>{}); else if (ct == 3) launch(RT_, int_c<3>{}); else launch(RT_, int_c<4>{}); };
+    if (rt == 2) cols(int_c<2>{}); else cols(int_c<1>{});
     if (!ATOMA_CHECK_LAUNCH("linear_fp8w_mma_kernel")) return -1;
-    if (p.partial) {
-        const int out_n = p.epilogue == 2 ? p.n / 2 : p.n;
-        hipLaunchKernelGGL((linear_fp8w_reduce_kernel<T>), dim3((unsigned)cdiv((int64_t)p.batch * out_n, 1024)), dim3(256), 0, stream, p);
-        if (!ATOMA_CHECK_LAUNCH("linear_fp8w_reduce_kernel")) return -1;
-    }
-    return 0;
+    return !p.partial || launch_reduce<T, true>(p, stream) ? 0 : -1;
 }
 
-template <typename T> static int launch_fp8w(LinearFp8wParams &p, hipStream_t stream) {
+template <typename T> static int launch_fp8w(LinearParams &p, hipStream_t stream) {
     if (p.batch <= std::min(fp8w_gemv_max_batch, 4)) return launch_fp8w_gemv<T>(p, stream);
     if (p.batch <= std::min(fp8w_wg_max_batch, 16)) return launch_fp8w_wg<T>(p, stream);
     return launch_fp8w_mma<T>(p, stream);
@@ -579,18 +433,7 @@ static int linear_fp8w_entry(const void *x, const void *w8, const void *w_scale,
         set_error("linear_decode_fp8w: batch must be in [0, 64] (the fp8-weight kernels serve the decode range only; more than 64 rows is not supported)");
         return -1;
     }
-    if (in_features <= 0 || in_features % 128 != 0) { set_error("linear_decode_fp8w: in_features must be a positive multiple of 128"); return -1; }
-    if (out_features <= 0 || out_features % 16 != 0) { set_error("linear_decode_fp8w: out_features must be a positive multiple of 16"); return -1; }
-    if (epilogue == 2 && out_features % 32 != 0) { set_error("linear_decode_fp8w: the silu.up epilogue needs out_features to be a multiple of 32"); return -1; }
-    const int64_t y_width = epilogue == 2 ? out_features / 2 : out_features;
-    if (epilogue == 1 && (!aux || aux_row_stride < out_features || aux_row_stride % 4 || (reinterpret_cast<uintptr_t>(aux) & 7u))) {
-        set_error("linear_decode_fp8w: the residual epilogue needs an 8-byte aligned [batch, out_features] tensor");
-        return -1;
-    }
-    if (x_row_stride < in_features || w8_row_stride < in_features || y_row_stride < y_width) {
-        set_error("linear_decode_fp8w: row strides must cover a row");
-        return -1;
-    }
+    if (!check_linear_args("linear_decode_fp8w", in_features, out_features, x_row_stride, w8_row_stride, y_row_stride, epilogue, aux, aux_row_stride)) return -1;
     if (x_row_stride % 8 || y_row_stride % 4) { set_error("linear_decode_fp8w: strides must keep rows 16-byte (x) / 8-byte (y) aligned"); return -1; }
     if (w8_row_stride % 16) { set_error("linear_decode_fp8w: w8_row_stride (bytes) must be a multiple of 16"); return -1; }
     if (!x || !w8 || !y || (reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w8)) & 15u || reinterpret_cast<uintptr_t>(y) & 7u) {
@@ -604,14 +447,8 @@ static int linear_fp8w_entry(const void *x, const void *w8, const void *w_scale,
         return -1;
     }
     if (batch == 0) return 0;
-    LinearFp8wParams p{};
-    p.x = static_cast<const uint16_t *>(x);
-    p.w = static_cast<const uint8_t *>(w8);
+    LinearParams p = linear_params_of(x, w8, y, batch, in_features, out_features, x_row_stride, w8_row_stride, y_row_stride, epilogue, aux, aux_row_stride);
     p.w_scale = static_cast<const float *>(w_scale);
-    p.y = static_cast<uint16_t *>(y);
-    p.x_row_stride = x_row_stride; p.w_row_stride = w8_row_stride; p.y_row_stride = y_row_stride;
-    p.batch = (int)batch; p.n = (int)out_features; p.k = (int)in_features;
-    p.epilogue = epilogue; p.aux = static_cast<const uint16_t *>(aux); p.aux_row_stride = aux_row_stride;
     const auto s = static_cast<hipStream_t>(stream);
     return dtype == ATOMA_BF16 ? launch_fp8w<bf16_t>(p, s) : launch_fp8w<f16_t>(p, s);
 }

@@ -98,13 +98,13 @@ struct LtDevice {
 static const size_t LT_WORKSPACE_BYTES = 64u << 20;
 static const int LT_MAX_CANDIDATES = 128, LT_TIMED_REPS = 10;
 // how many of the library's candidate algorithms are timed on first use of a problem (ATOMA_LINEAR_CANDIDATES, 1..128)
-static const int LT_CANDIDATES = [] { const char *e = getenv("ATOMA_LINEAR_CANDIDATES"); const int n = e ? atoi(e) : 16; return n < 1 ? 1 : (n > LT_MAX_CANDIDATES ? LT_MAX_CANDIDATES : n); }();
+static const int LT_CANDIDATES = [] { const int n = env_int("ATOMA_LINEAR_CANDIDATES", 16); return n < 1 ? 1 : (n > LT_MAX_CANDIDATES ? LT_MAX_CANDIDATES : n); }();
 // time the library's candidate algorithms on first use of a problem (ATOMA_LINEAR_AUTOTUNE=0: take the heuristic's first choice)
-static const int linear_autotune = getenv("ATOMA_LINEAR_AUTOTUNE") ? atoi(getenv("ATOMA_LINEAR_AUTOTUNE")) : 1;
+static const int linear_autotune = env_int("ATOMA_LINEAR_AUTOTUNE", 1);
 static std::mutex *g_lt_mu = new std::mutex;
 static std::map<int, LtDevice> *g_lt_devices = new std::map<int, LtDevice>;
 
-static const int lt_debug = getenv("ATOMA_LINEAR_DEBUG") ? atoi(getenv("ATOMA_LINEAR_DEBUG")) : 0;
+static const int lt_debug = env_int("ATOMA_LINEAR_DEBUG", 0);
 #define LT_DBG(...) do { if (lt_debug) { fprintf(stderr, "[lt] " __VA_ARGS__); fputc('\n', stderr); fflush(stderr); } } while (0)
 static bool lt_ok(hipblasStatus_t st, const char *what) {
     if (st == HIPBLAS_STATUS_SUCCESS) return true;
@@ -272,7 +272,7 @@ int release_gemm_workspaces() {
 }
 
 // batches up to this many rows take the weight-streaming kernel (measured crossover, tools/bench_kernels.py linear)
-static const int linear_stream_max_batch = getenv("ATOMA_LINEAR_STREAM_MAX_BATCH") ? atoi(getenv("ATOMA_LINEAR_STREAM_MAX_BATCH")) : 4;
+static const int linear_stream_max_batch = env_int("ATOMA_LINEAR_STREAM_MAX_BATCH", 4);
 
 }  // namespace atoma
 

@@ -1,4 +1,5 @@
-// Shared by the projection kernels (linear_decode.hip, linear_tile.hip): operand types, the 16x16x32 MFMA wrapper, kernel parameters.
+// Shared by the projection kernels (linear_decode.hip, linear_fp8w.hip, linear_tile.hip, linear_wide.hip): operand types, the 16x16x32 MFMA wrapper,
+// kernel parameters.  The shared device code is in linear_stream.h, the launchers' shared planning in linear_plan.h.
 #pragma once
 #include "common.h"
 
@@ -20,7 +21,7 @@ template <> __device__ __forceinline__ lf32x4 lin_mfma<f16_t>(const lu32x4 &a, c
 }
 
 struct LinearParams {
-    const uint16_t *x, *w;
+    const uint16_t *x, *w;       // w: [n][k] in the activations' dtype; fp8 weights (linear_fp8w.hip): e4m3fn BYTES behind this pointer, w_row_stride in bytes
     uint16_t *y;
     float *partial;              // [splits][batch][n] fp32, or null when splits == 1
     int64_t x_row_stride, w_row_stride, y_row_stride;   // elements
@@ -30,8 +31,8 @@ struct LinearParams {
     int64_t aux_row_stride;
     const uint16_t *norm_w;      // non-null: x is RMS-normalised with this weight [k] on the way in (linear_gemv_kernel<.., NORM>)
     float norm_eps;
+    const float *w_scale;        // fp8 weights: one f32 scale per output feature [n], applied to the fp32 sum where it is rounded; null otherwise
 };
-
 
 // linear_tile.hip: the LDS-DMA tile kernel for 17..64 rows.  0 = launched (p.partial set when more than two K splits left fp32 partials:
 // the caller runs linear_reduce_kernel), 1 = shape not served, -1 = error.  dtype: ATOMA_F16 / ATOMA_BF16.

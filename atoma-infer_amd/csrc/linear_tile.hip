@@ -19,7 +19,7 @@
 // partials for the caller's reduce / RoPE kernel.  fp32 accumulation in K order (split 0 + split 1 + ..), one rounding, then the epilogue
 // with the reference's rounding points -- the same for the paired and the plain kernel on the same matrix.  Epilogues: none / residual
 // add / SiLU.up (MODE 1) / RoPE + KV-cache write (MODE 2, atoma_linear_decode_qkv_rope_cache).
-#include "linear_params.h"
+#include "linear_stream.h"
 #include "sync_ticket.h"
 #include <algorithm>
 #include <atomic>
@@ -277,10 +277,7 @@ __global__ void __launch_bounds__(512, 1) linear_tile_kernel(const TileParams tp
         const lf32x4 up = xch[ct * 64 + lane];
         float v[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float g = round_through<T>(acc[0][i]);
-            v[i] = round_through<T>(g / (1.f + __expf(-g))) * round_through<T>(up[i]);
-        }
+        for (int i = 0; i < 4; ++i) v[i] = silu_round<T>(round_through<T>(acc[0][i])) * round_through<T>(up[i]);
         uint2 o;
         o.x = pack2<T>(v[0], v[1]);
         o.y = pack2<T>(v[2], v[3]);
@@ -288,15 +285,12 @@ __global__ void __launch_bounds__(512, 1) linear_tile_kernel(const TileParams tp
         return;
     }
     if (brow >= p.batch) return;
-    if constexpr (MODE == TILE_GATE_UP && GPW >= 2) {              // rounding points as in linear_reduce_kernel
+    if constexpr (MODE == TILE_GATE_UP && GPW >= 2) {              // rounding points as in linear_store4
 #pragma unroll
         for (int a = 0; a < GPW / 2; ++a) {
             float v[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float g = round_through<T>(acc[a][i]);
-                v[i] = round_through<T>(g / (1.f + __expf(-g))) * round_through<T>(acc[a + GPW / 2][i]);
-            }
+            for (int i = 0; i < 4; ++i) v[i] = silu_round<T>(round_through<T>(acc[a][i])) * round_through<T>(acc[a + GPW / 2][i]);
             uint2 o;
             o.x = pack2<T>(v[0], v[1]);
             o.y = pack2<T>(v[2], v[3]);
@@ -304,29 +298,15 @@ __global__ void __launch_bounds__(512, 1) linear_tile_kernel(const TileParams tp
         }
     } else if constexpr (MODE == TILE_PLAIN) {
 #pragma unroll
-        for (int a = 0; a < GPW; ++a) {
-            const int n = n0 + grow[a] + 4 * grp;
-            float v[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = round_through<T>(acc[a][i]);
-            if (p.epilogue == 1) {
-                const uint2 rr = *reinterpret_cast<const uint2 *>(p.aux + (int64_t)brow * p.aux_row_stride + n);
-                v[0] += lo_to_f32<T>(rr.x); v[1] += hi_to_f32<T>(rr.x); v[2] += lo_to_f32<T>(rr.y); v[3] += hi_to_f32<T>(rr.y);
-            }
-            uint2 o;
-            o.x = pack2<T>(v[0], v[1]);
-            o.y = pack2<T>(v[2], v[3]);
-            *reinterpret_cast<uint2 *>(p.y + (int64_t)brow * p.y_row_stride + n) = o;
-        }
+        for (int a = 0; a < GPW; ++a) linear_store4<T>(p, brow, n0 + grow[a] + 4 * grp, acc[a]);
     }
 }
 
-static int tile_env_or(const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; }
 // knobs: environment at load time, atoma_set_option("linear_tile*") at run time (A/B runs inside one process)
-static std::atomic<int> linear_tile_on{tile_env_or("ATOMA_LINEAR_TILE", 1)};          // 0: the older kernels serve 17..64 rows
-static std::atomic<int> linear_tile_nw{tile_env_or("ATOMA_LINEAR_TILE_NW", 0)};       // weight rows per workgroup: 0 = by shape
-static std::atomic<int> linear_tile_splits{tile_env_or("ATOMA_LINEAR_TILE_SPLITS", 0)};   // K splits: 0 = by shape
-static std::atomic<int> linear_tile_max_splits{tile_env_or("ATOMA_LINEAR_TILE_MAX_SPLITS", 8)};   // largest split the plan considers (A/B: 4 = round 3's plans)
+static std::atomic<int> linear_tile_on{env_int("ATOMA_LINEAR_TILE", 1)};          // 0: the older kernels serve 17..64 rows
+static std::atomic<int> linear_tile_nw{env_int("ATOMA_LINEAR_TILE_NW", 0)};       // weight rows per workgroup: 0 = by shape
+static std::atomic<int> linear_tile_splits{env_int("ATOMA_LINEAR_TILE_SPLITS", 0)};   // K splits: 0 = by shape
+static std::atomic<int> linear_tile_max_splits{env_int("ATOMA_LINEAR_TILE_MAX_SPLITS", 8)};   // largest split the plan considers (A/B: 4 = round 3's plans)
 bool set_linear_tile_option(const std::string &name, int value) {
     if (name == "linear_tile") linear_tile_on = value;
     else if (name == "linear_tile_nw") linear_tile_nw = value;
@@ -422,7 +402,7 @@ template <typename T> static int launch_linear_tile_t(LinearParams &p, hipStream
         if (!p.partial) return -1;
     }
     tp.p = p;
-    static const int w_nt = tile_env_or("ATOMA_LINEAR_TILE_W_NT", 1);
+    static const int w_nt = env_int("ATOMA_LINEAR_TILE_W_NT", 1);
     tp.w_plain = w_nt ? 0 : 1;
     if (rope) tp.rope = *rope;
     const int mode = rope ? TILE_ROPE : (p.epilogue == 2 ? TILE_GATE_UP : TILE_PLAIN);

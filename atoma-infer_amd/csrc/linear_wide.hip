@@ -19,7 +19,7 @@
 // fp32 accumulation in K order, one rounding, then the epilogue with the reference's rounding points (none / residual add / SiLU.up /
 // RoPE + KV-cache write) -- bit-identical to the plain projection followed by the separate op, because the plan (rows per workgroup, K
 // split) comes from the shape of W alone.
-#include "linear_params.h"
+#include "linear_stream.h"
 #include "sync_ticket.h"
 #include <algorithm>
 #include <atomic>
@@ -294,15 +294,12 @@ __global__ void __launch_bounds__(512, 1) linear_wide_kernel(const WideParams tp
                 put(y1, col0);
                 put(y2, col0 + half);
             }
-        } else if constexpr (MODE == WIDE_GATE_UP) {               // rounding points as in linear_reduce_kernel
+        } else if constexpr (MODE == WIDE_GATE_UP) {               // rounding points as in linear_store4
 #pragma unroll
             for (int a = 0; a < GPW / 2; ++a) {
                 float v[4];
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float g = round_through<T>(acc[a][b][i]);
-                    v[i] = round_through<T>(g / (1.f + __expf(-g))) * round_through<T>(acc[a + GPW / 2][b][i]);
-                }
+                for (int i = 0; i < 4; ++i) v[i] = silu_round<T>(round_through<T>(acc[a][b][i])) * round_through<T>(acc[a + GPW / 2][b][i]);
                 uint2 o;
                 o.x = pack2<T>(v[0], v[1]);
                 o.y = pack2<T>(v[2], v[3]);
@@ -310,20 +307,7 @@ __global__ void __launch_bounds__(512, 1) linear_wide_kernel(const WideParams tp
             }
         } else {
 #pragma unroll
-            for (int a = 0; a < GPW; ++a) {
-                const int n = n0 + grow[a] + 4 * grp;
-                float v[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] = round_through<T>(acc[a][b][i]);
-                if (p.epilogue == 1) {
-                    const uint2 rr = *reinterpret_cast<const uint2 *>(p.aux + (int64_t)brow * p.aux_row_stride + n);
-                    v[0] += lo_to_f32<T>(rr.x); v[1] += hi_to_f32<T>(rr.x); v[2] += lo_to_f32<T>(rr.y); v[3] += hi_to_f32<T>(rr.y);
-                }
-                uint2 o;
-                o.x = pack2<T>(v[0], v[1]);
-                o.y = pack2<T>(v[2], v[3]);
-                *reinterpret_cast<uint2 *>(p.y + (int64_t)brow * p.y_row_stride + n) = o;
-            }
+            for (int a = 0; a < GPW; ++a) linear_store4<T>(p, brow, n0 + grow[a] + 4 * grp, acc[a][b]);
         }
     }
 }
@@ -420,10 +404,7 @@ __global__ void __launch_bounds__(512, 1) linear_wide_gu112_kernel(const WidePar
         const lf32x4 gate = hi ? got : acc[g][0], up = hi ? acc[g][1] : got;
         float v[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {                                  // rounding points as in linear_reduce_kernel / the 128-row kernel
-            const float x = round_through<T>(gate[i]);
-            v[i] = round_through<T>(x / (1.f + __expf(-x))) * round_through<T>(up[i]);
-        }
+        for (int i = 0; i < 4; ++i) v[i] = silu_round<T>(round_through<T>(gate[i])) * round_through<T>(up[i]);   // rounding points as in linear_store4
         uint2 o;
         o.x = pack2<T>(v[0], v[1]);
         o.y = pack2<T>(v[2], v[3]);
@@ -431,15 +412,14 @@ __global__ void __launch_bounds__(512, 1) linear_wide_gu112_kernel(const WidePar
     }
 }
 
-static int wide_env_or(const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; }
 // knobs: environment at load time, atoma_set_option("linear_wide*") at run time (A/B runs inside one process)
-static std::atomic<int> linear_wide_on{wide_env_or("ATOMA_LINEAR_WIDE", 1)};           // 0: linear_big_kernel serves 65..256 rows
-static std::atomic<int> linear_wide_nw{wide_env_or("ATOMA_LINEAR_WIDE_NW", 0)};        // weight rows per workgroup: 0 = by shape
-static std::atomic<int> linear_wide_splits{wide_env_or("ATOMA_LINEAR_WIDE_SPLITS", 0)};   // K splits: 0 = by shape
-static std::atomic<int> linear_wide_var{wide_env_or("ATOMA_LINEAR_WIDE_VAR", 0)};      // probe bits, see WideParams::var
-static std::atomic<int> linear_wide_bb{wide_env_or("ATOMA_LINEAR_WIDE_BB", 0)};        // batch blocks: 0 = by shape, 1 = one tile over the batch, 2 = blocks of 128 rows
-static std::atomic<int> linear_wide_gu112{wide_env_or("ATOMA_LINEAR_WIDE_GU112", 1)};  // 0: gate/up + SiLU.up always on the 128-row tiles
-static std::atomic<int> linear_wide_xcd{wide_env_or("ATOMA_LINEAR_WIDE_XCD", 0)};      // 1: a K range per XCD (splits 2 / 4 / 8) -- measured slower (o 25.2 vs 23.7 us, down 53.4 vs 52.0): off
+static std::atomic<int> linear_wide_on{env_int("ATOMA_LINEAR_WIDE", 1)};           // 0: linear_big_kernel serves 65..256 rows
+static std::atomic<int> linear_wide_nw{env_int("ATOMA_LINEAR_WIDE_NW", 0)};        // weight rows per workgroup: 0 = by shape
+static std::atomic<int> linear_wide_splits{env_int("ATOMA_LINEAR_WIDE_SPLITS", 0)};   // K splits: 0 = by shape
+static std::atomic<int> linear_wide_var{env_int("ATOMA_LINEAR_WIDE_VAR", 0)};      // probe bits, see WideParams::var
+static std::atomic<int> linear_wide_bb{env_int("ATOMA_LINEAR_WIDE_BB", 0)};        // batch blocks: 0 = by shape, 1 = one tile over the batch, 2 = blocks of 128 rows
+static std::atomic<int> linear_wide_gu112{env_int("ATOMA_LINEAR_WIDE_GU112", 1)};  // 0: gate/up + SiLU.up always on the 128-row tiles
+static std::atomic<int> linear_wide_xcd{env_int("ATOMA_LINEAR_WIDE_XCD", 0)};      // 1: a K range per XCD (splits 2 / 4 / 8) -- measured slower (o 25.2 vs 23.7 us, down 53.4 vs 52.0): off
 bool set_linear_wide_option(const std::string &name, int value) {
     if (name == "linear_wide") linear_wide_on = value;
     else if (name == "linear_wide_nw") linear_wide_nw = value;

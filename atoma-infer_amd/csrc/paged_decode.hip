@@ -980,10 +980,6 @@ int decode_num_splits(int64_t waves_per_split, int max_seqlen_k, int waves_per_c
 //   decode_p            ATOMA_DECODE_P            tiles in flight per wave (2..4)
 //   decode_nt           ATOMA_DECODE_NT           0/1 non-temporal K/V loads
 //   decode_stream       ATOMA_DECODE_STREAM       balanced mode for large batches with device-side lengths (decode_run_items): 0 off, 1 default, 2 always, 3 ragged only
-static int env_int(const char *name, int dflt) {
-    const char *v = getenv(name);
-    return v ? atoi(v) : dflt;
-}
 // One OS thread per GPU calls into the library (model_executor.rs:428): the knobs are relaxed atomics, initialised once
 // (function-local static), so a set_option from one thread never tears a read on another.
 typedef std::atomic<int> opt_int;

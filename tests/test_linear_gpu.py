@@ -78,6 +78,39 @@ def test_linear_decode_exact_cases_and_linearity(gpu):
     assert np.array_equal(gpu_linear(gpu, xr, eye, BF16), xr)
 
 
+@pytest.mark.parametrize("B,N", [(1, 64), (4, 64), (5, 64), (17, 64), (17, 48)])
+def test_stream_pipeline_every_tail_length(gpu, B, N):
+    """The software pipeline the streaming kernels share (ATOMA_STREAM_PIPELINE), at every length of its guarded paths, through the plain
+    entries (no epilogue: the paired instantiations are not reached here).  K = 128.m for m = 1..13 and m = 16 gives every wavefront of the
+    16-bit kernels 1 .. 2P + 1 chunks for P = 2 and 3, with one wavefront per workgroup and, from K = 1024 on, two; with fp8 weights the unit
+    is a 256-input slab (the half slab of odd m included): 1 .. 7 slabs with one wavefront, and two wavefronts at K = 2048 only.  B = 4 takes
+    the fp8 gemv kernel's P = 2 form; N = 48 sends 17 rows to linear_decode_kernel (64 features go to the tile kernel).
+    Integer-valued inputs, |x| <= 4, |w| <= 2, K <= 2048: every partial sum is an integer of magnitude <= 16384, exact in fp32 in any
+    association order, so the result must equal the oracle's bit for bit -- a chunk dropped or taken twice by a tail cannot hide."""
+    from oracle import fp8_oracle as F8
+    from oracle.halfs import from_f32
+    from fp8w_ref import linear_fp8w
+    rng = np.random.default_rng(1000 * B + N)
+    for m in list(range(1, 14)) + [16]:
+        K = 128 * m
+        xf = rng.integers(-4, 5, (B, K)).astype(np.float32)
+        wf = rng.integers(-2, 3, (N, K)).astype(np.float32)
+        for dtype in (BF16, F16):
+            x, w = from_f32(xf, dtype), from_f32(wf, dtype)
+            ref = LO.linear(x, w, dtype)
+            assert np.isfinite(to_f32(ref, dtype)).all() and ref.any()
+            assert np.array_equal(gpu_linear(gpu, x, w, dtype), ref), (m, dtype)
+            w8, scale = F8.encode(wf), np.ones(N, np.float32)
+            ref8 = linear_fp8w(x, w8, scale, dtype)
+            assert np.array_equal(ref8, ref)                 # fp8 holds these weights exactly
+            dx, dw, ds = gpu.DeviceBuffer.from_numpy(x), gpu.DeviceBuffer.from_numpy(w8), gpu.DeviceBuffer.from_numpy(scale)
+            dy = gpu.DeviceBuffer(B * N * 2)
+            dy.fill_bytes(0xFF)
+            assert gpu.lib.atoma_linear_decode_fp8w(dx.ptr, dw.ptr, ds.ptr, dy.ptr, B, K, N, K, K, N, dtype, None) == 0, gpu.last_error()
+            gpu.synchronize()
+            assert np.array_equal(dy.numpy(np.uint16, (B, N)), ref8), (m, dtype, "fp8 weights")
+
+
 def test_linear_decode_rejects_bad_arguments(gpu):
     d = gpu.DeviceBuffer(1 << 16)
     call = lambda B=1, K=128, N=16, xs=None, dt=BF16: gpu.lib.atoma_linear_decode(d.ptr, d.ptr, d.ptr, B, K, N, xs or K, K, N, dt, None)
@@ -193,7 +226,9 @@ def test_linear_decode_65_to_256_rows(gpu, dtype, B, K, N):
 
 @pytest.mark.parametrize("opts", [dict(linear_wide_nw=64, linear_wide_splits=1), dict(linear_wide_nw=128, linear_wide_splits=1), dict(linear_wide_nw=64, linear_wide_splits=2),
                                   dict(linear_wide_nw=128, linear_wide_splits=3), dict(linear_wide_nw=64, linear_wide_splits=4), dict(linear_wide_nw=128, linear_wide_splits=8),
-                                  dict(linear_wide_nw=64, linear_wide_splits=4, linear_wide_xcd=0), dict(linear_wide_nw=128, linear_wide_splits=5), dict(linear_wide=0)])
+                                  dict(linear_wide_nw=64, linear_wide_splits=4, linear_wide_xcd=0), dict(linear_wide_nw=128, linear_wide_splits=5), dict(linear_wide=0),
+                                  dict(linear_wide_nw=64, linear_wide_splits=2, linear_wide_xcd=1), dict(linear_wide_nw=64, linear_wide_splits=4, linear_wide_xcd=1),
+                                  dict(linear_wide_nw=128, linear_wide_splits=8, linear_wide_xcd=1)])
 @pytest.mark.parametrize("B", [65, 128, 129, 160, 192, 200, 256])
 def test_linear_wide_every_tile_shape_and_split(gpu, opts, B):
     """linear_wide_kernel (round 6: 65..256 rows): every template variant (64 / 128 weight rows x 128 / 256 batch rows), K unsplit and
@@ -205,7 +240,7 @@ def test_linear_wide_every_tile_shape_and_split(gpu, opts, B):
     K, N = 2048, 1152                                   # 1152 = 9 x 128 = 18 x 64: a tile count no XCD group divides
     L = gpu.lib
     names = ("linear_wide", "linear_wide_nw", "linear_wide_splits", "linear_wide_xcd")
-    defaults = dict(linear_wide=1, linear_wide_nw=0, linear_wide_splits=0, linear_wide_xcd=1)
+    defaults = dict(linear_wide=1, linear_wide_nw=0, linear_wide_splits=0, linear_wide_xcd=0)
     try:
         for n in names:
             assert L.atoma_set_option(n.encode(), opts.get(n, defaults[n])) == 0
