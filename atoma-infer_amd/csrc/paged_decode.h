@@ -1,5 +1,5 @@
-// Shared device-side pieces of the decode kernels (paged_decode.hip: 16-bit caches; paged_decode_fp8.hip: fp8 caches):
-// parameters, the wavefront -> work mapping, the balanced mode, small lane helpers.  See paged_decode.hip for the design.
+// Shared pieces of the decode kernels (paged_decode.hip: 16-bit caches; paged_decode_fp8.hip: fp8 caches): parameters, the
+// wavefront -> work mapping, the balanced mode, small lane helpers, the launchers' template dispatch.  See paged_decode.hip for the design.
 #pragma once
 #include "attn_params.h"
 #include "sync_ticket.h"
@@ -410,6 +410,18 @@ template <bool STREAM, int NWG = 1, typename F, typename M = DecodeNoMerge> __de
             }
         }
     }
+}
+
+// Host: run-time launch choices handed to a generic lambda as compile-time constants (as dispatch_nw in linear_plan.h).
+// dispatch_bool: f(std::true_type / std::false_type); decode_dispatch<PMAX>: f(NT, P) with P = min(tiles in flight, PMAX), at least 2.
+template <typename F> static inline void dispatch_bool(bool b, F &&f) {
+    if (b) f(std::true_type{}); else f(std::false_type{});
+}
+template <int PMAX, typename F> static inline void decode_dispatch(bool nt, int tiles, F &&f) {
+    dispatch_bool(nt, [&](auto NT) {
+        if constexpr (PMAX >= 4) { if (tiles >= 4) return f(NT, std::integral_constant<int, 4>{}); }
+        if (tiles >= 3) f(NT, std::integral_constant<int, 3>{}); else f(NT, std::integral_constant<int, 2>{});
+    });
 }
 
 template <int I, int N, typename F> __device__ __forceinline__ void decode_static_for(F &&f) {

@@ -417,7 +417,7 @@ __device__ __forceinline__ void paged_decode_mqk_item(const DecodeParams &p, con
         const bool has_alibi = p.alibi_slopes != nullptr;
         const float alibi = (has_alibi && col < nq) ? p.alibi_slopes[b * p.alibi_batch_stride + hq0 + col] * 1.4426950408889634f : 0.f;
 
-        // ---- loader (page ids through the scalar cache, buffer loads: see paged_decode_kernel) ----
+        // ---- loader: page ids through the scalar cache, buffer loads ----
         const bool paged = p.block_table != nullptr;
         const uint32_t tpp = paged ? (uint32_t)(p.page_size >> 4) : 1u;
         const uint32_t tpp_magic = tpp > 1 ? (uint32_t)((0x100000000ull + tpp - 1) / tpp) : 0u;
@@ -536,11 +536,11 @@ __device__ __forceinline__ void paged_decode_mqk_item(const DecodeParams &p, con
             }
         };
 
-        // ---- software pipeline: P tiles in flight per wave (see paged_decode_kernel) ----
+        // ---- software pipeline: P tiles in flight per wave, unconditional steady state, guarded start and tail ----
         u32x4 kb[P][4], vb[P][4];
         int pid[P];
         int t = t0;
-        const int steady_end = min(t1, L >> 4);   // a ragged last tile takes the clamped loads (see paged_decode_item)
+        const int steady_end = min(t1, L >> 4);   // a ragged last tile takes the clamped loads (paged too: never-written slots)
         if (t0 + 2 * P <= steady_end) {
 #pragma unroll
             for (int s = 0; s < P; ++s) pid[s] = fetch_pid(t0 + s);
@@ -690,6 +690,7 @@ __global__ void __launch_bounds__(64 * NWG, 2) paged_decode_wg_kernel(const Deco
     wk.t0 = wk.split * per;
     wk.t1 = min(wk.t0 + per, wk.n_tiles);
     wk.partial = true;
+    wk.balanced = false;
     wk.prow = 0;
     wk.sink_o = &s_o[wave][0][0];
     wk.sink_lse = &s_lse[wave][0];
@@ -1156,11 +1157,11 @@ static void launch_decode_mqk(DecodeParams &p, hipStream_t stream) {
     // 3 tiles in flight for every group size since P.V runs on the matrix cores (32 accumulator registers whatever G; option decode_mqk_p8:
     // tiles in flight at 8 q heads per wavefront, A/B)
     static const int p8 = env_int("ATOMA_DECODE_MQK_P8", 3);
-    const bool p3 = decode_options().p >= 3 && (G <= 4 || p8 >= 3), nt = decode_options().nt != 0;
+    const int tiles = decode_options().p >= 3 && (G <= 4 || p8 >= 3) ? 3 : 2;
+    const bool nt = decode_options().nt != 0;
     if constexpr (!PAIR64) {
         if (decode_wg_applicable(p)) {
-            if (nt) { if (p3) launch_decode_wg<T, 128, G, 3, true, true>(p, stream); else launch_decode_wg<T, 128, G, 2, true, true>(p, stream); }
-            else { if (p3) launch_decode_wg<T, 128, G, 3, false, true>(p, stream); else launch_decode_wg<T, 128, G, 2, false, true>(p, stream); }
+            decode_dispatch<3>(nt, tiles, [&](auto NT, auto P) { launch_decode_wg<T, 128, G, P.value, NT.value, true>(p, stream); });
             return;
         }
     }
@@ -1172,25 +1173,23 @@ static void launch_decode_mqk(DecodeParams &p, hipStream_t stream) {
             (pair_opt == 2 || (units >= (int64_t)device_num_cus() * 6 && units <= (int64_t)device_num_cus() * 8 && (pair_opt == 1 || decode_hint_says_ragged(p.b))))) {
             p.stream_waves = 0;
             const dim3 grid((unsigned)(((int64_t)p.b + 1) / 2 * (p.h_k * p.gchunks / 4)));
-            note_decode_kernel("paged_decode_pair_kernel", decode_tname<T>(), 128, G, p3 ? 3 : 2, nt, "two sequences per workgroup, halves merged in LDS");
-            if (nt) { if (p3) hipLaunchKernelGGL((paged_decode_pair_kernel<T, G, 3, true>), grid, dim3(512), 0, stream, p); else hipLaunchKernelGGL((paged_decode_pair_kernel<T, G, 2, true>), grid, dim3(512), 0, stream, p); }
-            else { if (p3) hipLaunchKernelGGL((paged_decode_pair_kernel<T, G, 3, false>), grid, dim3(512), 0, stream, p); else hipLaunchKernelGGL((paged_decode_pair_kernel<T, G, 2, false>), grid, dim3(512), 0, stream, p); }
+            note_decode_kernel("paged_decode_pair_kernel", decode_tname<T>(), 128, G, tiles, nt, "two sequences per workgroup, halves merged in LDS");
+            decode_dispatch<3>(nt, tiles, [&](auto NT, auto P) { hipLaunchKernelGGL((paged_decode_pair_kernel<T, G, P.value, NT.value>), grid, dim3(512), 0, stream, p); });
             ATOMA_CHECK_LAUNCH("paged_decode_pair_kernel");
             return;
         }
     }
     const int64_t blocks = (int64_t)p.b * p.num_splits * p.h_k * p.gchunks;
     if (p.stream_waves > 0) set_stream_waves(p, 8, stream);   // __launch_bounds__(64, 2)
-    note_decode_kernel(PAIR64 ? "paged_decode_mqk_kernel(kv-head pairs)" : "paged_decode_mqk_kernel", decode_tname<T>(), PAIR64 ? 64 : 128, G, p3 ? 3 : 2, nt,
+    note_decode_kernel(PAIR64 ? "paged_decode_mqk_kernel(kv-head pairs)" : "paged_decode_mqk_kernel", decode_tname<T>(), PAIR64 ? 64 : 128, G, tiles, nt,
                        p.stream_waves > 0 ? "balanced" : (p.num_splits > 1 ? (std::to_string(p.num_splits) + " KV splits + combine").c_str() : "one wavefront per (sequence, kv head)"));
-#define ATOMA_MQK(P_, NT_, S_) hipLaunchKernelGGL((paged_decode_mqk_kernel<T, G, P_, NT_, S_, PAIR64>), dim3((unsigned)blocks), dim3(64), 0, stream, p)
-#define ATOMA_MQK_S(P_, NT_) do { if (p.stream_waves > 0) ATOMA_MQK(P_, NT_, true); else ATOMA_MQK(P_, NT_, false); } while (0)
     // (4 and 5 tiles in flight for the 8-head groups of split-KV launches, 8 / 16 / 32 splits, in-launch merge or combine kernel: all within
     // 29.3-32 us on the 70B shard's B = 64 call -- profiles/r04_decode_b64_hk1_depth_probe.txt; launch, ramp and merge bound it, not depth)
-    if (nt) { if (p3) ATOMA_MQK_S(3, true); else ATOMA_MQK_S(2, true); }
-    else { if (p3) ATOMA_MQK_S(3, false); else ATOMA_MQK_S(2, false); }
-#undef ATOMA_MQK_S
-#undef ATOMA_MQK
+    decode_dispatch<3>(nt, tiles, [&](auto NT, auto P) {
+        dispatch_bool(p.stream_waves > 0, [&](auto STREAM) {
+            hipLaunchKernelGGL((paged_decode_mqk_kernel<T, G, P.value, NT.value, STREAM.value, PAIR64>), dim3((unsigned)blocks), dim3(64), 0, stream, p);
+        });
+    });
     if (!ATOMA_CHECK_LAUNCH("paged_decode_mqk_kernel")) return;
     if (p.num_splits > 1 || (p.stream_waves > 0 && !p.line_merge)) {   // (cut probe: line_merge = 2 skips this launch too)
         hipLaunchKernelGGL((decode_combine_kernel<T, PAIR64 ? 64 : 128>), dim3((unsigned)std::min<int64_t>((int64_t)p.b * p.h, combine_grid_cap())), dim3(64), 0, stream, p);
@@ -1203,24 +1202,15 @@ static void launch_decode_tdg(DecodeParams &p, hipStream_t stream) {
     // tiles in flight per wave / waves per SIMD the register budget is capped for: G = 8 at
     // D = 128 needs more than 256 VGPRs (64 for O, 32 for q, 64 per K+V pair in flight).
     constexpr int MINW = (G >= 8 && D >= 128) ? 1 : 2;
-    const int cfg_p = decode_options().p, cfg_nt = decode_options().nt;
-    const int P = (G >= 8 && cfg_p > 2) ? 2 : cfg_p;
+    const bool nt = decode_options().nt != 0;
+    const int cfg_p = decode_options().p, tiles = (G >= 8 && cfg_p > 2) ? 2 : cfg_p;
     if constexpr (MINW == 2) {                   // (the 8-head dot2 variant needs the 512 registers of one wavefront per SIMD)
         if (decode_wg_applicable(p)) {
-            if (cfg_nt) { if (P >= 3) launch_decode_wg<T, D, G, 3, true, false>(p, stream); else launch_decode_wg<T, D, G, 2, true, false>(p, stream); }
-            else { if (P >= 3) launch_decode_wg<T, D, G, 3, false, false>(p, stream); else launch_decode_wg<T, D, G, 2, false, false>(p, stream); }
+            decode_dispatch<3>(nt, tiles, [&](auto NT, auto P) { launch_decode_wg<T, D, G, P.value, NT.value, false>(p, stream); });
             return;
         }
     }
-    if (cfg_nt) {
-        if (P >= 4) launch_decode_cfg<T, D, G, 4, MINW, true>(p, stream);
-        else if (P == 3) launch_decode_cfg<T, D, G, 3, MINW, true>(p, stream);
-        else launch_decode_cfg<T, D, G, 2, MINW, true>(p, stream);
-    } else {
-        if (P >= 4) launch_decode_cfg<T, D, G, 4, MINW, false>(p, stream);
-        else if (P == 3) launch_decode_cfg<T, D, G, 3, MINW, false>(p, stream);
-        else launch_decode_cfg<T, D, G, 2, MINW, false>(p, stream);
-    }
+    decode_dispatch<4>(nt, tiles, [&](auto NT, auto P) { launch_decode_cfg<T, D, G, P.value, MINW, NT.value>(p, stream); });
     if (!ATOMA_CHECK_LAUNCH("paged_decode_kernel")) return;
     if (p.num_splits > 1 || (p.stream_waves > 0 && !p.line_merge)) {
         hipLaunchKernelGGL((decode_combine_kernel<T, D>), dim3((unsigned)std::min<int64_t>((int64_t)p.b * p.h, combine_grid_cap())), dim3(64), 0, stream, p);

@@ -34,6 +34,46 @@ template <typename T> __device__ __forceinline__ void fp8x16_to_pairs(const u32x
     out[6] = fp8x2_to_pair<T>(v.w, false); out[7] = fp8x2_to_pair<T>(v.w, true);
 }
 
+// Where a 16-token tile of the fp8 cache lives, for both item functions below: one byte per element (strides in bytes), always paged.  Page ids
+// are scalar loads clamped to the pages the sequence owns; the loads themselves and their lane offsets stay in the kernels.
+struct Fp8TileSource {
+    uint32_t tpp, tpp_magic;                     // tiles per page, and its reciprocal for __umulhi
+    int last_pg;
+    const int *bt_row;
+    const char *kbase, *vbase;
+    int64_t k_row_bytes, v_row_bytes, k_page_bytes, v_page_bytes;
+
+    __device__ __forceinline__ Fp8TileSource(const DecodeParams &p, const DecodeWork &wk) {
+        tpp = (uint32_t)(p.page_size >> 4);
+        tpp_magic = tpp > 1 ? (uint32_t)((0x100000000ull + tpp - 1) / tpp) : 0u;
+        last_pg = (wk.L + p.page_size - 1) / p.page_size - 1;
+        bt_row = p.block_table + (int64_t)wk.b * p.block_table_batch_stride;
+        kbase = reinterpret_cast<const char *>(p.k) + (int64_t)wk.hk * p.k_head_stride;
+        vbase = reinterpret_cast<const char *>(p.v) + (int64_t)wk.hk * p.v_head_stride;
+        k_row_bytes = p.k_row_stride, v_row_bytes = p.v_row_stride;
+        k_page_bytes = p.k_batch_stride, v_page_bytes = p.v_batch_stride;
+    }
+    __device__ __forceinline__ int page_of(int tile, uint32_t &tip) const {  // wave-uniform
+        if (tpp == 1) { tip = 0; return tile; }
+        const uint32_t pg = __umulhi((uint32_t)tile, tpp_magic);
+        tip = (uint32_t)tile - pg * tpp;
+        return (int)pg;
+    }
+    __device__ __forceinline__ int fetch_pid(int tile) const {  // scalar load, always in bounds
+        uint32_t tip;
+        const int pg = min(page_of(tile, tip), last_pg);
+        return load_ro(bt_row + pg);
+    }
+    __device__ __forceinline__ void tile_rsrcs(int tile, int pid, __amdgpu_buffer_rsrc_t &kr, __amdgpu_buffer_rsrc_t &vr) const {
+        uint32_t tip;
+        (void)page_of(tile, tip);
+        const char *kt = kbase + (int64_t)pid * k_page_bytes + (int64_t)(tip << 4) * k_row_bytes;
+        const char *vt = vbase + (int64_t)pid * v_page_bytes + (int64_t)(tip << 4) * v_row_bytes;
+        kr = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(kt), 0, 0x7fffffff, 0x00020000);
+        vr = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(vt), 0, 0x7fffffff, 0x00020000);
+    }
+};
+
 template <typename T, int G, int P, bool NT>
 __device__ __forceinline__ void paged_decode_fp8_item(const DecodeParams &p, const DecodeWork &wk) {
     constexpr int D = 128;
@@ -70,36 +110,16 @@ __device__ __forceinline__ void paged_decode_fp8_item(const DecodeParams &p, con
             qv[gq][0] = a.x; qv[gq][1] = a.y; qv[gq][2] = a.z; qv[gq][3] = a.w;
             qv[gq][4] = c.x; qv[gq][5] = c.y; qv[gq][6] = c.z; qv[gq][7] = c.w;
         }
-        // ---- loader: as paged_decode_item, strides in BYTES (one byte per element) ----
-        const uint32_t tpp = (uint32_t)(p.page_size >> 4);
-        const uint32_t tpp_magic = tpp > 1 ? (uint32_t)((0x100000000ull + tpp - 1) / tpp) : 0u;
-        const int last_pg = (L + p.page_size - 1) / p.page_size - 1;
-        const int *bt_row = p.block_table + (int64_t)b * p.block_table_batch_stride;
-        const char *kbase = reinterpret_cast<const char *>(p.k) + (int64_t)hk * p.k_head_stride;
-        const char *vbase = reinterpret_cast<const char *>(p.v) + (int64_t)hk * p.v_head_stride;
-        const int64_t k_row_bytes = p.k_row_stride, v_row_bytes = p.v_row_stride;
-        const int64_t k_page_bytes = p.k_batch_stride, v_page_bytes = p.v_batch_stride;
+        // ---- loader: strides in BYTES (one byte per element) ----
+        const Fp8TileSource src(p, wk);
+        const int64_t k_row_bytes = src.k_row_bytes, v_row_bytes = src.v_row_bytes;
         const uint32_t k_lane_off = (uint32_t)(sub * k_row_bytes + dc * 16);
         const uint32_t v_lane_off = (uint32_t)(sub * v_row_bytes + dc * 16);
-        auto page_of = [&](int tile, uint32_t &tip) -> int {
-            if (tpp == 1) { tip = 0; return tile; }
-            const uint32_t pg = __umulhi((uint32_t)tile, tpp_magic);
-            tip = (uint32_t)tile - pg * tpp;
-            return (int)pg;
-        };
-        auto fetch_pid = [&](int tile) -> int {
-            uint32_t tip;
-            const int pg = min(page_of(tile, tip), last_pg);
-            return load_ro(bt_row + pg);
-        };
+        auto fetch_pid = [&](int tile) { return src.fetch_pid(tile); };
         constexpr int AUX = NT ? 2 : 0;
         auto issue = [&](u32x4 (&kb)[2], u32x4 (&vb)[2], int tile, int pid) {   // paged tiles always own their 16 rows
-            uint32_t tip;
-            (void)page_of(tile, tip);
-            const char *kt = kbase + (int64_t)pid * k_page_bytes + (int64_t)(tip << 4) * k_row_bytes;
-            const char *vt = vbase + (int64_t)pid * v_page_bytes + (int64_t)(tip << 4) * v_row_bytes;
-            const __amdgpu_buffer_rsrc_t kr = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(kt), 0, 0x7fffffff, 0x00020000);
-            const __amdgpu_buffer_rsrc_t vr = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(vt), 0, 0x7fffffff, 0x00020000);
+            __amdgpu_buffer_rsrc_t kr, vr;
+            src.tile_rsrcs(tile, pid, kr, vr);
 #pragma unroll
             for (int r = 0; r < 2; ++r) kb[r] = __builtin_amdgcn_raw_buffer_load_b128(kr, k_lane_off, (int)(r * RPI * k_row_bytes), AUX);
 #pragma unroll
@@ -330,39 +350,19 @@ __device__ __forceinline__ void paged_decode_fp8_mma_item(const DecodeParams &p,
                 qb[s4] = *reinterpret_cast<const u32x4 *>(p.q + (int64_t)b * p.q_batch_stride + (int64_t)(hq0 + col) * p.q_head_stride +
                                                           64 * (s4 >> 1) + 16 * grp + 8 * (s4 & 1));
         }
-        const uint32_t tpp = (uint32_t)(p.page_size >> 4);
-        const uint32_t tpp_magic = tpp > 1 ? (uint32_t)((0x100000000ull + tpp - 1) / tpp) : 0u;
-        const int last_pg = (L + p.page_size - 1) / p.page_size - 1;
-        const int *bt_row = p.block_table + (int64_t)b * p.block_table_batch_stride;
-        const char *kbase = reinterpret_cast<const char *>(p.k) + (int64_t)hk * p.k_head_stride;
-        const char *vbase = reinterpret_cast<const char *>(p.v) + (int64_t)hk * p.v_head_stride;
-        const int64_t k_row_bytes = p.k_row_stride, v_row_bytes = p.v_row_stride;
-        const int64_t k_page_bytes = p.k_batch_stride, v_page_bytes = p.v_batch_stride;
+        const Fp8TileSource src(p, wk);
+        const int64_t k_row_bytes = src.k_row_bytes, v_row_bytes = src.v_row_bytes;
         const bool klines = FP8_KLINES && (p.fp8_klines >= 2 || (p.fp8_klines == 1 && !wk.balanced && p.h_k > 1));
         const uint32_t k_lane_off = klines ? (uint32_t)((col & 7) * k_row_bytes + (grp + 4 * (col >> 3)) * 16)   // + 8 jj rows
                                            : (uint32_t)(col * k_row_bytes + grp * 16);                          // + 64 j
         const int k_step = klines ? (int)(8 * k_row_bytes) : 64;
         const uint32_t v_lane_off = (uint32_t)(4 * grp * v_row_bytes + col * 8);                                 // + i rows
-        auto page_of = [&](int tile, uint32_t &tip) -> int {
-            if (tpp == 1) { tip = 0; return tile; }
-            const uint32_t pg = __umulhi((uint32_t)tile, tpp_magic);
-            tip = (uint32_t)tile - pg * tpp;
-            return (int)pg;
-        };
-        auto fetch_pid = [&](int tile) -> int {
-            uint32_t tip;
-            const int pg = min(page_of(tile, tip), last_pg);
-            return load_ro(bt_row + pg);
-        };
+        auto fetch_pid = [&](int tile) { return src.fetch_pid(tile); };
         constexpr int AUX = NT ? 2 : 0;
         typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
         auto issue = [&](u32x4 (&kb)[2], u32x2 (&vb)[4], int tile, int pid) {
-            uint32_t tip;
-            (void)page_of(tile, tip);
-            const char *kt = kbase + (int64_t)pid * k_page_bytes + (int64_t)(tip << 4) * k_row_bytes;
-            const char *vt = vbase + (int64_t)pid * v_page_bytes + (int64_t)(tip << 4) * v_row_bytes;
-            const __amdgpu_buffer_rsrc_t kr = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(kt), 0, 0x7fffffff, 0x00020000);
-            const __amdgpu_buffer_rsrc_t vr = __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(vt), 0, 0x7fffffff, 0x00020000);
+            __amdgpu_buffer_rsrc_t kr, vr;
+            src.tile_rsrcs(tile, pid, kr, vr);
 #pragma unroll
             for (int j = 0; j < 2; ++j) kb[j] = __builtin_amdgcn_raw_buffer_load_b128(kr, k_lane_off, j * k_step, AUX);
 #pragma unroll
@@ -556,9 +556,9 @@ static void launch_fp8_tns(const DecodeParams &p, int G, bool mqk, bool wg8, int
 }
 template <typename T>
 static void launch_fp8_t(const DecodeParams &p, int G, bool nt, bool mqk, bool wg8, int64_t blocks, hipStream_t stream) {
-    const bool balanced = p.stream_waves > 0;
-    if (nt) { if (balanced) launch_fp8_tns<T, true, true>(p, G, mqk, wg8, blocks, stream); else launch_fp8_tns<T, true, false>(p, G, mqk, wg8, blocks, stream); }
-    else { if (balanced) launch_fp8_tns<T, false, true>(p, G, mqk, wg8, blocks, stream); else launch_fp8_tns<T, false, false>(p, G, mqk, wg8, blocks, stream); }
+    dispatch_bool(nt, [&](auto NT) {
+        dispatch_bool(p.stream_waves > 0, [&](auto STREAM) { launch_fp8_tns<T, NT.value, STREAM.value>(p, G, mqk, wg8, blocks, stream); });
+    });
 }
 void launch_fp8_kernels(const DecodeParams &p, int G, bool is_bf16, bool nt, bool mqk, bool wg8, int64_t blocks, hipStream_t stream) {
     if (is_bf16) launch_fp8_t<bf16_t>(p, G, nt, mqk, wg8, blocks, stream);

@@ -5,7 +5,8 @@ import numpy as np
 import pytest
 
 from oracle import attn_oracle as A
-from oracle.halfs import F16, BF16, to_f32
+from oracle import fp8_oracle as F8
+from oracle.halfs import F16, BF16, to_f32, from_f32
 from util import rand_half, make_paged_cache, assert_close, c_attention, ATOL_VS_F32, attn_atol, poison_unwritten_slots
 
 pytestmark = pytest.mark.gpu
@@ -682,3 +683,78 @@ def test_decode_other_head_sizes_streaming_kernel(gpu, d, dtype):
         for i, L in enumerate(ld):
             assert_close(out[i], ref[i], dtype, atol=attn_atol(dtype, int(L)), what=f"d={d} contiguous seq {i}")
 
+
+
+# ---- the tile pipelines of the four decode item functions at every length of their guarded and steady paths ----------------------------------------
+PIPE_D, PIPE_PAGE = 128, 16
+PIPE_LENS = np.array(sorted({16 * n for n in range(11)} | {16 * n - 5 for n in range(1, 11)}), np.int32)     # 0 .. 2 P + 2 tiles for P <= 4
+_pipe_cache = {}
+
+
+def _pipeline_case(hk, dtype, lens):
+    """q = 0 (every score 0, every p 1), K random, V[token][e] = 1 where e == tile of the token: O[e] = (tokens of the sequence in tile e) / L, so
+    a dropped tile moves its element from >= 0.1 to 0 and a doubled one by as much.  Built once per (hk, dtype, lengths); the oracle is checked
+    against the closed form here, on the CPU, before any kernel is compared with it."""
+    key = (hk, dtype, tuple(int(x) for x in lens))
+    if key not in _pipe_cache:
+        rng = np.random.default_rng(hk * 5 + dtype)
+        nb = int(sum((int(L) + PIPE_PAGE - 1) // PIPE_PAGE for L in lens)) + 2
+        kc, vc, bt = make_paged_cache(rng, nb, PIPE_PAGE, hk, PIPE_D, dtype, lens)
+        one = from_f32(np.float32([1.0]), dtype)[0]
+        vc[:] = 0
+        want = np.zeros((len(lens), PIPE_D), np.float32)
+        for b, L in enumerate(lens):
+            for t in range(int(L)):
+                vc[bt[b, t // PIPE_PAGE], t % PIPE_PAGE, :, (t // 16) % PIPE_D] = one
+                want[b, (t // 16) % PIPE_D] += 1.0 / L
+        q = np.zeros((len(lens), 1, 8, PIPE_D), np.uint16)
+        ref = A.flash_attn_kv_cache(q, kc, vc, np.float32(PIPE_D ** -0.5), dtype, bt, lens, mode="f32")
+        assert np.abs(to_f32(ref, dtype)[:, 0] - want[:, None, :]).max() <= 2.0 ** -8, "the oracle itself misses the closed form"
+        _pipe_cache[key] = (kc, vc, bt, ref)
+    return _pipe_cache[key]
+
+
+@pytest.mark.parametrize("dtype", [BF16, F16], ids=["bf16", "f16"])
+@pytest.mark.parametrize("kernel,h,hk,depth", [("dot2", 8, 8, 2), ("dot2", 8, 8, 3), ("dot2", 8, 8, 4), ("mqk", 8, 2, 2), ("mqk", 8, 2, 3),
+                                               ("fp8_dot2", 8, 2, 4), ("fp8_mma", 8, 2, 4)])
+def test_decode_pipeline_every_tile_count(gpu, kernel, h, hk, depth, dtype):
+    """The software pipeline of each decode item function (16-bit dot2 and matrix-core, fp8 dot2 and matrix-core; each has its own written-out
+    copy of the same loops) at 0 .. 2 P + 2 tiles, full and ragged last tile, with one wavefront per sequence; then split into pieces that start
+    at t0 > 0.  The inputs make a lost or repeated tile an error of >= 0.1 in one output element.  Pages of 16 tokens only: pages of several
+    tiles are the business of test_decode_matches_oracle_ragged and test_decode_fp8_matches_oracle_ragged."""
+    from test_kv_fp8_gpu import gpu_decode_fp8
+    opts = {b"decode_stream": 0, b"decode_min_tiles": 1 << 20, b"decode_p": depth, b"decode_mqk": 3 if kernel == "mqk" else 0,
+            b"decode_fp8_mqk": 1 if kernel == "fp8_mma" else 0}
+    name_of = {"dot2": "paged_decode_kernel<", "mqk": "paged_decode_mqk_kernel<", "fp8_dot2": "paged_decode_fp8_kernel<", "fp8_mma": "paged_decode_fp8_mma_kernel<"}
+    scale = np.float32(PIPE_D ** -0.5)
+
+    def run(lens):
+        kc, vc, bt, ref = _pipeline_case(hk, dtype, lens)
+        q = np.zeros((len(lens), 1, h, PIPE_D), np.uint16)
+        if kernel.startswith("fp8"):       # 0 and 1 are exact in e4m3 (v_scale = 1); K: any finite codes
+            k8 = F8.quantize(kc.reshape(-1, hk, PIPE_D), dtype, np.ones(hk, np.float32)).reshape(kc.shape)
+            v8 = F8.quantize(vc.reshape(-1, hk, PIPE_D), dtype, np.ones(hk, np.float32)).reshape(vc.shape)
+            out = gpu_decode_fp8(gpu, q[:, 0], k8, v8, np.ones(hk, np.float32), np.ones(hk, np.float32), bt, lens, scale, dtype)[:, None]
+            lse = None
+        else:
+            out, lse = gpu_decode(gpu, q, kc, vc, bt, lens, scale, dtype)
+        name = gpu.lib.atoma_last_decode_kernel().decode()
+        assert name.startswith(name_of[kernel]) and f",P={depth}," in name, name
+        for i, L in enumerate(lens):
+            assert_close(out[i], ref[i], dtype, atol=attn_atol(dtype, int(L)), what=f"{name}: L={L} ({(int(L) + 15) // 16} tiles)")
+            if lse is not None:
+                assert np.isposinf(lse[i]).all() if L == 0 else np.allclose(lse[i], np.log(np.float32(L)), rtol=1e-4, atol=1e-4), (name, int(L), lse[i])
+        assert not out[lens == 0].any(), "empty sequence must produce exact zeros"
+        return name
+
+    try:
+        for k, v in opts.items():
+            assert gpu.lib.atoma_set_option(k, v) == 0
+        name = run(PIPE_LENS)
+        assert "one wavefront per (sequence, kv head)" in name, name
+        assert gpu.lib.atoma_set_option(b"decode_min_tiles", 1) == 0
+        name = run(PIPE_LENS[-2:])
+        assert "KV splits" in name, name
+    finally:
+        for k, v in {b"decode_stream": 1, b"decode_min_tiles": 8, b"decode_p": 3, b"decode_mqk": 29, b"decode_fp8_mqk": 1}.items():
+            gpu.lib.atoma_set_option(k, v)
