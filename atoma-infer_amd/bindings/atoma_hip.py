@@ -150,6 +150,10 @@ _opt("atoma_linear_decode_fp8w", [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i
 _opt("atoma_linear_decode_fp8w_residual", [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp])
 _opt("atoma_linear_decode_fp8w_silu_mul", [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp])
 _opt("atoma_quantize_weight_fp8", [_vp, _i64, _i64, _i64, _int, _vp, _i64, _vp, _vp])
+_opt("atoma_linear_decode_mxfp4", [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp])
+_opt("atoma_linear_decode_mxfp4_residual", [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp])
+_opt("atoma_linear_decode_mxfp4_silu_mul", [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp])
+_opt("atoma_quantize_weight_mxfp4", [_vp, _i64, _i64, _i64, _int, _vp, _i64, _vp, _i64, _vp])
 _opt("atoma_linear", [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp])
 _opt("atoma_topk_rows", [_vp, _i64, _i64, _i64, _int, _i64, _vp, _vp, _vp])
 _opt("atoma_sample_rows", [_vp, _i64, _i64, _i64, _int, _f32, _i64, _f32, _vp, _vp, _vp, _vp])

@@ -288,6 +288,39 @@ int atoma_linear_decode_fp8w_silu_mul(const void *x, const void *w8_gate_up, con
 int atoma_quantize_weight_fp8(const void *w, int64_t out_features, int64_t in_features, int64_t w_row_stride, int dtype, void *w8_out,
                               int64_t w8_row_stride, float *scale_out, void *stream);
 
+/* MXFP4 (OCP microscaling FP4) WEIGHTS for the same projections, "W4A16": 4-bit e2m1 elements with one e8m0 power-of-two scale per block of
+ * 32 inputs, 0.53 bytes per weight -- the layout pre-quantised checkpoints ship ([.., K/32, 16] block bytes + [.., K/32] scales, row-major:
+ * such a checkpoint passes its own bytes unchanged).  w4 [out_features, in_features / 2] bytes: byte i of a row holds input 2i in its low
+ * nibble and input 2i + 1 in its high nibble; bit 3 of a nibble is the sign, bits 0..2 index {0, 0.5, 1, 1.5, 2, 3, 4, 6}.  w_scale
+ * [out_features, in_features / 32] bytes: byte s means 2^(s - 127) for inputs 32j .. 32j + 31.
+ *   y[b][n] = round_dtype(sum_k x[b][k] * e2m1(nibble[n][k]) * 2^(w_scale[n][k / 32] - 127))     fp32 accumulation, one rounding
+ * Defined when every non-zero weight value is a finite normal number of dtype; outside that (scale bytes 0xff, 0 and the like) the
+ * affected output column is unspecified, nothing faults and no other column is disturbed.  batch in [0, 16] (more is an error); batch == 0
+ * or out_features == 0 (intermediate == 0) return 0 without a launch once the entry's own checks have passed (out_features < 0 is an error);
+ * in_features % 128 == 0, out_features % 16 == 0 (% 32 for _silu_mul); x / y / residual row strides in elements; w4_row_stride in BYTES,
+ * at least in_features / 2, a multiple of 16, w4 16-byte aligned; scale_row_stride in BYTES, at least in_features / 32, a multiple of 4,
+ * w_scale 4-byte aligned.  _residual and _silu_mul keep the rounding points of atoma_linear_decode_residual / _silu_mul (w4 and w_scale
+ * cover the stacked gate rows, then the up rows) and are bit-identical to the plain call followed by atoma_add / atoma_silu_mul. */
+int atoma_linear_decode_mxfp4(const void *x, const void *w4, const void *w_scale, void *y, int64_t batch, int64_t in_features,
+                              int64_t out_features, int64_t x_row_stride, int64_t w4_row_stride, int64_t scale_row_stride,
+                              int64_t y_row_stride, int dtype, void *stream);
+int atoma_linear_decode_mxfp4_residual(const void *x, const void *w4, const void *w_scale, const void *residual, void *y, int64_t batch,
+                                       int64_t in_features, int64_t out_features, int64_t x_row_stride, int64_t w4_row_stride,
+                                       int64_t scale_row_stride, int64_t residual_row_stride, int64_t y_row_stride, int dtype, void *stream);
+int atoma_linear_decode_mxfp4_silu_mul(const void *x, const void *w4_gate_up, const void *w_scale, void *y, int64_t batch, int64_t in_features,
+                                       int64_t intermediate, int64_t x_row_stride, int64_t w4_row_stride, int64_t scale_row_stride,
+                                       int64_t y_row_stride, int dtype, void *stream);
+
+/* 16-bit weights -> the MXFP4 form above, on the device.  Per row and block of 32 inputs: amax = max |f32(w)|; scale byte 127 when amax
+ * == 0, else e + 127 with e = floor(log2 amax) - 2 raised to at least -125 (bf16) / -13 (f16) so that 0.5 * 2^e stays a normal number;
+ * per element v = |f32(w)| * 2^-e (exact) -> the nearest of the eight magnitudes, ties to the even code, saturating at 6 (v <= 0.25: 0,
+ * < 0.75: 1, <= 1.25: 2, < 1.75: 3, <= 2.5: 4, < 3.5: 5, <= 5: 6, else 7); the sign bit is the source's.  Source weights are finite.
+ * w [out_features, in_features] of dtype, w_row_stride in elements (% 8), in_features % 32 == 0; w4_row_stride in bytes (% 16, at least
+ * in_features / 2), scale_row_stride in bytes (at least in_features / 32); w and w4_out 16-byte aligned.  Stream-ordered, no host
+ * synchronisation. */
+int atoma_quantize_weight_mxfp4(const void *w, int64_t out_features, int64_t in_features, int64_t w_row_stride, int dtype, void *w4_out,
+                                int64_t w4_row_stride, void *scale_out, int64_t scale_row_stride, void *stream);
+
 /* The RMSNorm in FRONT of a projection folded into it (llama.rs:402 -> 269-271 for q/k/v, :408 -> 364-365 for gate/up):
  * y = rms_norm(x; norm_weight, eps) . w^T, and the _silu_mul form of the stacked gate/up projection on top of that.  On the rows the
  * VALU streaming kernel serves (1 by default, ATOMA_LINEAR_GEMV_MAX_BATCH up to 2) the projection kernel derives each row's scale itself with atoma_rms_norm's own arithmetic and

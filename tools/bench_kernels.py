@@ -546,8 +546,9 @@ def bench_linear_fp8w():
             json.dump(doc, f, indent=1)
 
 
-def bench_step_fp8w():
-    """The Llama-3.1-8B decode step (context 4096, hipGraph replay) at batch 1 and 16: 16-bit weights against weight_dtype="fp8", same process."""
+def bench_step_fp8w(wds=("bf16", "fp8")):
+    """The Llama-3.1-8B decode step (context 4096, hipGraph replay) at batch 1 and 16: 16-bit weights against weight_dtype="fp8" (and "mxfp4"
+    when asked for), same process, interleaved."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import decode_step as DS
     rng = np.random.default_rng(9)
@@ -566,16 +567,16 @@ def bench_step_fp8w():
         slots = bt[np.arange(B), ctx // c.page].astype(np.int64) * c.page + ctx % c.page
         ids = rng.integers(0, c.vocab, B)
         graphs, steps = {}, {}
-        for wd in ("bf16", "fp8"):
+        for wd in wds:
             step = steps[wd] = DS.DecodeStep(c, B, B * pps + 2, pps, w, st, fused_epilogues=True, weight_dtype=wd)
             step.set_inputs(ids, ctx, slots, ctx + 1, bt)
             step.run(); st.synchronize()
             with ah.Graph.capture(st) as g:
                 step.run()
             graphs[wd] = g
-        times = {"bf16": [], "fp8": []}
+        times = {wd: [] for wd in wds}
         for _ in range(3):
-            for wd in ("bf16", "fp8"):
+            for wd in wds:
                 g = graphs[wd]
                 for _ in range(3):
                     g.launch()
@@ -590,10 +591,81 @@ def bench_step_fp8w():
         m16, m8 = float(np.median(times["bf16"])), float(np.median(times["fp8"]))
         rec = dict(batch=B, context=S, bf16_step_ms=round(m16, 4), fp8_step_ms=round(m8, 4), speedup=round(m16 / m8, 3),
                    bf16_step_ms_repeats=[round(t, 4) for t in times["bf16"]], fp8_step_ms_repeats=[round(t, 4) for t in times["fp8"]])
+        if "mxfp4" in wds:
+            m4 = float(np.median(times["mxfp4"]))
+            rec.update(mxfp4_step_ms=round(m4, 4), mxfp4_speedup_over_fp8=round(m8 / m4, 3), mxfp4_step_ms_repeats=[round(t, 4) for t in times["mxfp4"]])
         out.append(rec)
-        print(json.dumps(dict(workload=f"E2 Llama-3.1-8B decode step, 16-bit vs fp8 weights, batch={B}", **rec)), flush=True)
+        what = "16-bit vs fp8 weights" if tuple(wds) == ("bf16", "fp8") else "weights " + " / ".join(wds)
+        print(json.dumps(dict(workload=f"E2 Llama-3.1-8B decode step, {what}, batch={B}", **rec)), flush=True)
         del steps, graphs
     return out
+
+
+def bench_linear_mxfp4():
+    """MXFP4 weights against fp8 and 16-bit weights, the five Llama-3.1-8B projection shapes x batch 1, 2, 4, 8, 16: atoma_linear_decode_mxfp4,
+    atoma_linear_decode_fp8w and atoma_linear_decode timed interleaved on the same shape in the same process, three repeats.  All three rotate
+    through enough weight copies (> 600 MB of nibble bytes per set) that no call finds its weights in the 256 MB Infinity Cache.  Each call's
+    fraction of the HBM rate is on its own bytes: mxfp4 = N.K/2 + N.K/32 + 2.B.K + 2.B.N.  ATOMA_BENCH_MXFP4_OUT=path: the whole table as one
+    JSON document (profiles/mxfp4_linear.json); also runs the 8B step at batch 1 and 16 for all three weight types."""
+    rng = np.random.default_rng(8)
+    rows, repeats = [], 3
+    only = [t for t in os.environ.get("ATOMA_BENCH_MXFP4_SHAPES", "").split(",") if t]
+    batches = tuple(int(t) for t in os.environ.get("ATOMA_BENCH_MXFP4_BATCHES", "1,2,4,8,16").split(","))
+    for name, N, K in (("qkv", 6144, 4096), ("o", 4096, 4096), ("gate_up", 28672, 4096), ("down", 4096, 14336), ("lm_head", 128256, 4096)):
+        if only and name not in only:
+            continue
+        copies = max(2, -(-(600 << 20) // (N * K // 2)))
+        w16, w8, sc8, w4, sc4 = [], [], [], [], []
+        for i in range(copies):
+            w16.append(rand_dev(rng, N * K * 2))
+            w8.append(ah.DeviceBuffer(N * K)); sc8.append(ah.DeviceBuffer(N * 4))
+            w4.append(ah.DeviceBuffer(N * K // 2)); sc4.append(ah.DeviceBuffer(N * K // 32))
+            assert ah.lib.atoma_quantize_weight_fp8(w16[i].ptr, N, K, K, 1, w8[i].ptr, K, sc8[i].ptr, None) == 0, ah.last_error()
+            assert ah.lib.atoma_quantize_weight_mxfp4(w16[i].ptr, N, K, K, 1, w4[i].ptr, K // 2, sc4[i].ptr, K // 32, None) == 0, ah.last_error()
+        ah.synchronize()
+        for B in batches:
+            x, y = rand_dev(rng, B * K * 2), ah.DeviceBuffer(B * N * 2)
+            turn = [0]
+
+            def f4():
+                i = turn[0] = (turn[0] + 1) % copies
+                ah.lib.atoma_linear_decode_mxfp4(x.ptr, w4[i].ptr, sc4[i].ptr, y.ptr, B, K, N, K, K // 2, K // 32, N, 1, None)
+
+            def f8():
+                i = turn[0] = (turn[0] + 1) % copies
+                ah.lib.atoma_linear_decode_fp8w(x.ptr, w8[i].ptr, sc8[i].ptr, y.ptr, B, K, N, K, K, N, 1, None)
+
+            def f16():
+                i = turn[0] = (turn[0] + 1) % copies
+                ah.lib.atoma_linear_decode(x.ptr, w16[i].ptr, y.ptr, B, K, N, K, K, N, 1, None)
+            t = {"mxfp4": [], "fp8": [], "bf16": []}
+            for _ in range(repeats):
+                for key, fn in (("mxfp4", f4), ("fp8", f8), ("bf16", f16)):
+                    t[key].append(timeit(fn, iters=2 * copies if copies > 10 else 20))
+            m = {k: float(np.median(v)) for k, v in t.items()}
+            io = 2 * B * K + 2 * B * N
+            nbytes = {"mxfp4": N * K // 2 + N * K // 32 + io, "fp8": N * K + 4 * N + io, "bf16": 2 * N * K + io}
+            rec = dict(shape=name, N=N, K=K, batch=B, weight_copies=copies, speedup_over_fp8=round(m["fp8"] / m["mxfp4"], 3),
+                       speedup_over_bf16=round(m["bf16"] / m["mxfp4"], 3), spread=round(max((max(v) - min(v)) / m[k] for k, v in t.items()), 4))
+            for k in ("mxfp4", "fp8", "bf16"):
+                rec[k + "_us"] = round(m[k] * 1e3, 2)
+                rec[k + "_us_repeats"] = [round(v * 1e3, 2) for v in t[k]]
+                rec[k + "_bytes"] = nbytes[k]
+                rec[k + "_frac_hbm"] = round(nbytes[k] / (m[k] * 1e-3) / 1e9 / HBM, 4)
+            rows.append(rec)
+            print(json.dumps(dict(workload=f"L6 linear_decode_mxfp4 vs fp8 vs 16-bit {name} [{N} x {K}] batch={B}", **rec)), flush=True)
+        for b in w16 + w8 + sc8 + w4 + sc4:
+            b.free()
+    out = os.environ.get("ATOMA_BENCH_MXFP4_OUT")
+    if out:
+        steps = bench_step_fp8w(("bf16", "fp8", "mxfp4"))
+        doc = dict(command="ATOMA_BENCH_MXFP4_OUT=<this file> python tools/bench_kernels.py linear_mxfp4", device="MI355X", hbm_peak_GBps=HBM,
+                   note="times in microseconds (steps in ms), median of 3 interleaved repeats; spread = (max - min) / median of the repeats, the "
+                        "largest of the three sides; rotating weights (no call finds its weights in the Infinity Cache); frac_hbm on each call's "
+                        "own bytes; step = hipGraph replay of tools/decode_step.py",
+                   linear=rows, step=steps)
+        with open(out, "w") as f:
+            json.dump(doc, f, indent=1)
 
 
 def bench_linear_mid():

@@ -6,7 +6,8 @@ KV-cache write -> paged decode attention -> o projection -> residual -> RMSNorm 
 down projection -> residual] -> RMSNorm -> lm_head -> argmax.  q/k/v and gate/up weights are stored concatenated
 (row blocks of one matrix), which changes nothing in the arithmetic: every output row is an independent dot product.
 Projections: atoma_linear (weight streaming up to 4 rows, hipBLASLt above), or, with weight_dtype="fp8" (batch <= 64), fp8 weights
-quantised once at upload and atoma_linear_decode_fp8w[_residual / _silu_mul].  Everything is enqueued on one stream, so a step can be captured in a hipGraph.
+quantised once at upload and atoma_linear_decode_fp8w[_residual / _silu_mul], or, with weight_dtype="mxfp4" (batch <= 16), MXFP4 weights
+(e2m1 nibbles + e8m0 block scales) and atoma_linear_decode_mxfp4[_residual / _silu_mul].  Everything is enqueued on one stream, so a step can be captured in a hipGraph.
 """
 import os
 import sys
@@ -49,13 +50,20 @@ class DecodeStep:
         # weight_dtype="fp8": the q/k/v, o, gate/up and down weights as e4m3fn bytes with one f32 scale per output row, quantised ONCE here
         # (atoma_quantize_weight_fp8) and multiplied by atoma_linear_decode_fp8w[_residual / _silu_mul]; lm_head and the embedding stay 16-bit.
         # The fused-RMSNorm and fused q/k/v + RoPE + cache forms do not exist over fp8 weights: the norms and atoma_rope_qk_cache run on their own.
-        if weight_dtype not in ("bf16", "fp8"):
-            raise ValueError(f"DecodeStep: weight_dtype must be 'bf16' or 'fp8', not {weight_dtype!r}")
+        # weight_dtype="mxfp4": the same four weights as e2m1 nibbles [N, K / 2] with one e8m0 scale byte per 32 inputs [N, K / 32]
+        # (atoma_quantize_weight_mxfp4, atoma_linear_decode_mxfp4[_residual / _silu_mul]), at most 16 rows; everything else as for fp8.
+        if weight_dtype not in ("bf16", "fp8", "mxfp4"):
+            raise ValueError(f"DecodeStep: weight_dtype must be 'bf16', 'fp8' or 'mxfp4', not {weight_dtype!r}")
         self.fp8w = weight_dtype == "fp8"
+        self.mxfp4 = weight_dtype == "mxfp4"
         if self.fp8w and batch > 64:
             raise ValueError(f"DecodeStep(weight_dtype='fp8'): batch {batch} > 64 -- the fp8-weight projections serve at most 64 rows")
         if self.fp8w and allreduce is not None:
             raise ValueError("DecodeStep(weight_dtype='fp8'): tensor-parallel ranks are not supported with fp8 weights")
+        if self.mxfp4 and batch > 16:
+            raise ValueError(f"DecodeStep(weight_dtype='mxfp4'): batch {batch} > 16 -- the MXFP4-weight projections serve at most 16 rows")
+        if self.mxfp4 and allreduce is not None:
+            raise ValueError("DecodeStep(weight_dtype='mxfp4'): tensor-parallel ranks are not supported with MXFP4 weights")
         # allreduce_norm(in, residual, weight, x_out, norm_out, rows) -> True when it enqueued "x_out = residual + allreduce(in); norm_out =
         # RMSNorm(x_out) * weight" as ONE launch (atoma_xgmi_allreduce_add_rms_norm / atoma_allreduce_add_rms_norm); False = not available now:
         # the step falls back to allreduce + atoma_add_rms_norm (same bits)
@@ -80,17 +88,13 @@ class DecodeStep:
         self.fuse_norm = fuse_norm and not keep_intermediates and not self.fused   # residual add + the RMSNorm that follows it in one kernel
         self.w = weights                                   # dict of DeviceBuffers, see random_weights / upload_weights
         self.w8, self.w8_scale = {}, {}                    # fp8w: name -> per-layer DeviceBuffers (bytes [N, K]; f32 [N])
+        self.w4, self.w4_scale = {}, {}                    # mxfp4: name -> per-layer DeviceBuffers (nibble bytes [N, K / 2]; e8m0 bytes [N, K / 32])
         if self.fp8w:
-            self.qkv_fused = self.norm_in_proj = False
-            shapes = dict(wqkv=(c.qkv, c.hidden), wo=(c.hidden, c.h * c.d), wgu=(2 * c.inter, c.hidden), wdown=(c.hidden, c.inter))
-            for name, (n, k) in shapes.items():
-                self.w8[name], self.w8_scale[name] = [], []
-                for l in range(c.layers):
-                    w8, sc = ah.DeviceBuffer(n * k), ah.DeviceBuffer(n * 4)
-                    self._ok(ah.lib.atoma_quantize_weight_fp8(weights[name][l].ptr, n, k, k, BF16, w8.ptr, k, sc.ptr, stream.s), f"quantising {name}[{l}]")
-                    self.w8[name].append(w8)
-                    self.w8_scale[name].append(sc)
-            stream.synchronize()
+            self._quantise(weights, self.w8, self.w8_scale, lambda n, k: (n * k, n * 4),
+                           lambda w, n, k, q, sc: ah.lib.atoma_quantize_weight_fp8(w, n, k, k, BF16, q, k, sc, stream.s))
+        if self.mxfp4:
+            self._quantise(weights, self.w4, self.w4_scale, lambda n, k: (n * k // 2, n * k // 32),
+                           lambda w, n, k, q, sc: ah.lib.atoma_quantize_weight_mxfp4(w, n, k, k, BF16, q, k // 2, sc, k // 32, stream.s))
         page_elems = c.page * c.hk * c.d
         # kv_fp8: the KV cache holds e4m3fn bytes with one dequantisation scale per kv head (atoma_rope_qk_cache_fp8 /
         # atoma_paged_decode_fp8); everything else of the step is unchanged
@@ -128,6 +132,22 @@ class DecodeStep:
             greedy = np.zeros(B, ah.SAMPLING_PARAMS_DTYPE)
             greedy["temperature"], greedy["top_p"], greedy["repetition_penalty"] = 1.0, 1.0, 1.0
             self.params.upload(greedy)
+
+    def _quantise(self, weights, out, out_scale, sizes, quantise):
+        """The q/k/v, o, gate/up and down weights quantised once, at upload: sizes(n, k) -> (weight bytes, scale bytes) of one matrix,
+        quantise(w_ptr, n, k, out_ptr, scale_ptr) -> rc enqueues one matrix.  The fused-norm and fused q/k/v forms exist for 16-bit weights only."""
+        c = self.cfg
+        self.qkv_fused = self.norm_in_proj = False
+        shapes = dict(wqkv=(c.qkv, c.hidden), wo=(c.hidden, c.h * c.d), wgu=(2 * c.inter, c.hidden), wdown=(c.hidden, c.inter))
+        for name, (n, k) in shapes.items():
+            out[name], out_scale[name] = [], []
+            for l in range(c.layers):
+                nbytes, sbytes = sizes(n, k)
+                q, sc = ah.DeviceBuffer(nbytes), ah.DeviceBuffer(sbytes)
+                self._ok(quantise(weights[name][l].ptr, n, k, q.ptr, sc.ptr), f"quantising {name}[{l}]")
+                out[name].append(q)
+                out_scale[name].append(sc)
+        self.stream.synchronize()
 
     def _buf(self, name, layer, nbytes):
         key = (name, layer if self.keep else 0)
@@ -185,6 +205,8 @@ class DecodeStep:
         B, s = self.B, self.stream.s
         if self.fp8w:
             self._ok(ah.lib.atoma_linear_decode_fp8w(x.ptr, self.w8[name][l].ptr, self.w8_scale[name][l].ptr, y.ptr, B, K, N, K, K, N, BF16, s), what)
+        elif self.mxfp4:
+            self._ok(ah.lib.atoma_linear_decode_mxfp4(x.ptr, self.w4[name][l].ptr, self.w4_scale[name][l].ptr, y.ptr, B, K, N, K, K // 2, K // 32, N, BF16, s), what)
         else:
             self._ok(self.linear(x.ptr, self.w[name][l].ptr, y.ptr, B, K, N, K, K, N, BF16, s), what)
 
@@ -250,6 +272,12 @@ class DecodeStep:
                 self._ok(L.atoma_rms_norm(x1.ptr, self.w["norm2"][l].ptr, xn2.ptr, B, H, H, H, c.eps, BF16, s), "rms_norm")
                 self._ok(L.atoma_linear_decode_fp8w_silu_mul(xn2.ptr, w8["wgu"][l].ptr, sc["wgu"][l].ptr, act.ptr, B, H, c.inter, H, H, c.inter, BF16, s), "gate/up projection + silu * up")
                 self._ok(L.atoma_linear_decode_fp8w_residual(act.ptr, w8["wdown"][l].ptr, sc["wdown"][l].ptr, x1.ptr, x2.ptr, B, c.inter, H, c.inter, c.inter, H, H, BF16, s), "down projection + residual")
+            elif self.fused and self.mxfp4:
+                w4, sc = self.w4, self.w4_scale
+                self._ok(L.atoma_linear_decode_mxfp4_residual(att.ptr, w4["wo"][l].ptr, sc["wo"][l].ptr, x.ptr, x1.ptr, B, hd, H, hd, hd // 2, hd // 32, H, H, BF16, s), "o projection + residual")
+                self._ok(L.atoma_rms_norm(x1.ptr, self.w["norm2"][l].ptr, xn2.ptr, B, H, H, H, c.eps, BF16, s), "rms_norm")
+                self._ok(L.atoma_linear_decode_mxfp4_silu_mul(xn2.ptr, w4["wgu"][l].ptr, sc["wgu"][l].ptr, act.ptr, B, H, c.inter, H, H // 2, H // 32, c.inter, BF16, s), "gate/up projection + silu * up")
+                self._ok(L.atoma_linear_decode_mxfp4_residual(act.ptr, w4["wdown"][l].ptr, sc["wdown"][l].ptr, x1.ptr, x2.ptr, B, c.inter, H, c.inter, c.inter // 2, c.inter // 32, H, H, BF16, s), "down projection + residual")
             elif self.fused:
                 self._ok(L.atoma_linear_decode_residual(att.ptr, self.w["wo"][l].ptr, x.ptr, x1.ptr, B, hd, H, hd, hd, H, H, BF16, s), "o projection + residual")
                 if self.norm_in_proj:
