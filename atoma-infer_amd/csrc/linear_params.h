@@ -1,4 +1,4 @@
-// Shared by the projection kernels (linear_decode.hip, linear_fp8w.hip, linear_tile.hip, linear_wide.hip): operand types, the 16x16x32 MFMA wrapper,
+// Shared by the projection kernels (linear_decode.hip, linear_wq.h, linear_fp8w.hip, linear_tile.hip, linear_wide.hip): operand types, the 16x16x32 MFMA wrapper,
 // kernel parameters.  The shared device code is in linear_stream.h, the launchers' shared planning in linear_plan.h.
 #pragma once
 #include "common.h"
@@ -21,7 +21,7 @@ template <> __device__ __forceinline__ lf32x4 lin_mfma<f16_t>(const lu32x4 &a, c
 }
 
 struct LinearParams {
-    const uint16_t *x, *w;       // w: [n][k] in the activations' dtype; fp8 weights (linear_fp8w.hip): e4m3fn BYTES behind this pointer, w_row_stride in bytes
+    const uint16_t *x, *w;       // w: [n][k] in the activations' dtype; quantised weights (linear_wq.h): the format's BYTES behind this pointer, w_row_stride in bytes
     uint16_t *y;
     float *partial;              // [splits][batch][n] fp32, or null when splits == 1
     int64_t x_row_stride, w_row_stride, y_row_stride;   // elements

@@ -1,4 +1,4 @@
-// What the launchers of the streaming projection kernels share on the host (linear_decode.hip, linear_fp8w.hip), each thing once: the K-split plan
+// What the launchers of the streaming projection kernels share on the host (linear_decode.hip, linear_wq.h with linear_fp8w.hip and linear_mxfp4.hip), each thing once: the K-split plan
 // with its fp32 workspace, the launch of the kernel that adds the splits, the wavefronts per workgroup, their dispatch, and the argument checks.
 #pragma once
 #include "linear_stream.h"
@@ -32,7 +32,7 @@ template <typename T, bool SCALED = false> static inline bool launch_reduce(cons
 }
 
 // Wavefronts per workgroup of the single-launch kernels (the K split inside a workgroup): as many as keep waves_per_cu wavefronts per CU streaming,
-// each with at least 4 units (128-input chunks, or 256-input slabs of fp8 weights: 4 KiB per load round either way).  From the W rows, as above.
+// each with at least 4 units (128-input chunks, or the 4 KiB slabs of quantised weights, linear_wq.h: 4 KiB per load round either way).  From the W rows, as above.
 static inline int waves_per_workgroup(int64_t row_tiles, int64_t units, int waves_per_cu) {
     int nw = 1;
     while (nw < 8 && row_tiles * nw * 2 <= (int64_t)device_num_cus() * waves_per_cu && units / (nw * 2) >= 4) nw *= 2;

@@ -1,4 +1,4 @@
-// What the projection kernels share on the device (linear_decode.hip, linear_fp8w.hip, linear_tile.hip, linear_wide.hip), each thing once: the
+// What the projection kernels share on the device (linear_decode.hip, linear_wq.h with linear_fp8w.hip and linear_mxfp4.hip, linear_tile.hip, linear_wide.hip), each thing once: the
 // software pipeline of the weight-streaming kernels, the 16-lane row sum, the tile kernels' plain rounded store, and the kernel that adds K splits.
 #pragma once
 #include "linear_params.h"

@@ -1,6 +1,6 @@
 """fp8-weight projections on the device, through the C ABI: the quantiser bit for bit against the tests' restatement (fp8w_ref), the
-products against the exactly accumulated product under the acceptance rule of test_linear_gpu.check, the epilogues against the separate
-ops, strides, NaN bytes, stream order, and a whole decode step over fp8 weights op by op."""
+products against the exactly accumulated product under the acceptance rule of test_linear_gpu.check, one-hot inputs that pin every byte
+position, the epilogues against the separate ops, strides, NaN bytes, stream order, and a whole decode step over fp8 weights op by op."""
 import os
 import sys
 
@@ -11,12 +11,11 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 from oracle import elementwise_oracle as EO
 from oracle import fp8_oracle as F8
 from oracle import linear_oracle as LO
-from oracle import norm_rope_oracle as NR
-from oracle import cache_oracle as CO
 from oracle.halfs import F16, BF16, to_f32, from_f32
 from fp8w_ref import quantize_rows, linear_fp8w
 from test_linear_gpu import check
 from util import rand_half
+from wq_cases import report, unsigned_zero, check_decode_step_op_by_op
 
 pytestmark = pytest.mark.gpu
 
@@ -51,11 +50,6 @@ def gpu_fp8w(gpu, x, w8, scale, dtype, stream=None, sync=True):
         return dy, (dx, dw, ds)
     gpu.synchronize()
     return dy.numpy(np.uint16, (max(B, 1), N))[:B]
-
-
-def report(what, got, ref, dtype):
-    g, r = to_f32(got, dtype), to_f32(ref, dtype)
-    print(f"{what}: max |err| {np.abs(g - r).max() if g.size else 0.0:.3e}, differing {(got != ref).mean() if g.size else 0.0:.5f}")
 
 
 @pytest.mark.parametrize("dtype", [BF16, F16])
@@ -107,6 +101,34 @@ def test_linear_decode_fp8w_power_of_two_scales_meet_the_16_bit_oracle(gpu, dtyp
     got = gpu_fp8w(gpu, x, w8, scale, dtype)
     report(f"fp8w pow2 B={B} dtype={dtype}", got, LO.linear(x, dequant, dtype), dtype)
     check(got, LO.linear(x, dequant, dtype), dtype)
+
+
+@pytest.mark.parametrize("dtype", [BF16, F16])
+@pytest.mark.parametrize("B", [4, 16, 32])
+@pytest.mark.parametrize("K", [640, 2432])
+def test_linear_decode_fp8w_one_hot_inputs_pick_single_weights(gpu, dtype, B, K):
+    """x[b] = e_k(b): y[b][n] is decode(w8[n][k(b)]) * scale[n] to the bit -- the byte order of a load, the lane / piece / slab arithmetic and
+    the zeros of the half slab at the end (K = 640: 2.5 slabs in one wavefront; K = 2432: 9.5 slabs over two wavefronts, the half slab the last
+    of the second; B = 32: the 17..64-row kernel).  Neighbouring positions hold different codes and every non-NaN code occurs."""
+    N = 48
+    w8 = ((37 * np.arange(N)[:, None] + np.arange(K)[None, :]) % 256).astype(np.uint8)
+    w8[(w8 & 0x7F) == 0x7F] ^= 0x40                              # the two NaN codes -> 0x3F / 0xBF
+    assert len(np.unique(w8)) == 254 and (w8[:, 1:] != w8[:, :-1]).all()
+    scale = (2.0 ** (np.arange(N) % 5 - 2)).astype(np.float32)   # powers of two in [2^-2, 2^2]
+    W = F8.decode(w8).astype(np.float64) * scale[:, None]
+    ks = [0, 1, 7, 8, 15, 16, 127, 128, 255, 256, 257, 383, 384, 511, 512, K - 129, K - 128, K - 17, K - 1,
+          2, 9, 31, 32, 63, 64, 129, 254, 385, 400, 450, 500, K - 2, K - 16, K - 18, K - 127, K - 200, K - 64]
+    ks = list(dict.fromkeys(ks))[:32]                            # 32 distinct positions, the named ones first
+    assert len(ks) == 32 and len(ks) % B == 0 and max(ks) < K and {K - 129, K - 128, K - 17, K - 1} <= set(ks)
+    one = from_f32(np.array([1.0], np.float32), dtype)[0]
+    for i in range(0, len(ks), B):
+        x = np.zeros((B, K), np.uint16)
+        x[np.arange(B), ks[i:i + B]] = one
+        got = gpu_fp8w(gpu, x, w8, scale, dtype)
+        ref = from_f32(W[:, ks[i:i + B]].T.astype(np.float32), dtype)
+        assert np.array_equal(to_f32(ref, dtype).astype(np.float64), W[:, ks[i:i + B]].T)      # exact in the dtype
+        bad = np.argwhere(unsigned_zero(got) != unsigned_zero(ref))
+        assert bad.size == 0, f"k = {ks[i:i + B]}: first mismatch (b, n) = {bad[0]}, got {to_f32(got, dtype)[tuple(bad[0])]}, want {to_f32(ref, dtype)[tuple(bad[0])]}"
 
 
 @pytest.mark.parametrize("B,K,N", [(1, 2048, 2048), (3, 4096, 256), (4, 384, 4096), (9, 2048, 2048), (16, 14336, 512), (16, 640, 48),
@@ -197,92 +219,10 @@ def test_linear_decode_fp8w_rejects_more_than_64_rows_on_the_device(gpu):
     assert "64" in gpu.last_error()
 
 
-def close_linear(got, ref, what):                                # the rule of tests/test_decode_step_gpu.py:28
-    g, r = to_f32(got, BF16), to_f32(ref, BF16)
-    assert (np.abs(g - r) <= 2.0 ** -7 * np.abs(r) + 3e-5).all(), what
-
-
-def _step_setup(rng, B):
-    import decode_step as DS
-    cfg = DS.Config(layers=2, hidden=512, heads=4, kv_heads=2, head_dim=128, intermediate=1024, vocab=1008, page=16, max_pos=256)
-    ctx = rng.integers(0, 100, B)
-    lens = (ctx + 1).astype(np.int32)
-    blocks = [(int(n) + cfg.page - 1) // cfg.page for n in lens]
-    num_pages = sum(blocks) + 3
-    perm = rng.permutation(num_pages)
-    bt = np.zeros((B, max(blocks)), np.int32)
-    pos0 = 0
-    for i, n in enumerate(blocks):
-        bt[i, :n] = perm[pos0:pos0 + n]
-        pos0 += n
-    H, I = cfg.hidden, cfg.inter
-    near1 = lambda: NR.from_f32(1 + to_f32(rand_half(rng, (H,), BF16, 0.1), BF16), BF16)
-    host = dict(emb=rand_half(rng, (cfg.vocab, H), BF16), norm1=[near1() for _ in range(cfg.layers)],
-                wqkv=[rand_half(rng, (cfg.qkv, H), BF16, H ** -0.5) for _ in range(cfg.layers)],
-                wo=[rand_half(rng, (H, cfg.h * cfg.d), BF16, (cfg.h * cfg.d) ** -0.5) for _ in range(cfg.layers)],
-                norm2=[near1() for _ in range(cfg.layers)], wgu=[rand_half(rng, (2 * I, H), BF16, H ** -0.5) for _ in range(cfg.layers)],
-                wdown=[rand_half(rng, (H, I), BF16, I ** -0.5) for _ in range(cfg.layers)], norm_f=near1(),
-                lm_head=rand_half(rng, (cfg.vocab, H), BF16, H ** -0.5))
-    kc0 = [rand_half(rng, (num_pages, cfg.page, cfg.hk, cfg.d), BF16) for _ in range(cfg.layers)]
-    vc0 = [rand_half(rng, (num_pages, cfg.page, cfg.hk, cfg.d), BF16) for _ in range(cfg.layers)]
-    ids = rng.integers(0, cfg.vocab, B)
-    slots = np.array([CO.slot_mapping_for(bt[i], int(ctx[i]), int(ctx[i]) + 1, cfg.page)[0] for i in range(B)], np.int64)
-    return DS, cfg, host, (ids, ctx, slots, lens, bt), num_pages, kc0, vc0
-
-
 @pytest.mark.parametrize("B", [1, 8, 64])
 def test_decode_step_over_fp8_weights_op_by_op(gpu, B):
-    """DecodeStep(weight_dtype="fp8"): every projection's recorded output against the restatement applied to that op's own recorded input,
-    residual / SiLU.up results bit-equal to the element-wise oracles on the recorded operands, next_ids = argmax of the step's own logits,
-    the stored bytes / scales = the restatement's quantisation of the host weights; then the fused-epilogue run bit-equal to the unfused."""
-    rng = np.random.default_rng(40 + B)
-    DS, cfg, host, inputs, num_pages, kc0, vc0 = _step_setup(rng, B)
-    ids, ctx, slots, lens, bt = inputs
-    st = gpu.Stream()
-    w = DS.upload_weights(cfg, host)
-    H, I, hd, qw = cfg.hidden, cfg.inter, cfg.h * cfg.d, cfg.qkv
-    dl = lambda buf, shape: buf.numpy(np.uint16, shape)
-    runs = []
-    for fused in (False, True):
-        step = DS.DecodeStep(cfg, B, num_pages, bt.shape[1], w, st, keep_intermediates=not fused, fused_epilogues=fused, weight_dtype="fp8")
-        assert step.fp8w and step.fused == fused
-        for l in range(cfg.layers):
-            step.kc[l].upload(kc0[l])
-            step.vc[l].upload(vc0[l])
-        step.set_inputs(*inputs)
-        step.run()
-        st.synchronize()
-        runs.append((dl(step.logits, (B, cfg.vocab)), step.next_ids.numpy(np.int32, (B,)), [dl(step.kc[l], None) for l in range(cfg.layers)],
-                     [dl(step.vc[l], None) for l in range(cfg.layers)]))
-        if fused:
-            continue
-        q = {}
-        for name in ("wqkv", "wo", "wgu", "wdown"):
-            for l in range(cfg.layers):
-                q[name, l] = quantize_rows(host[name][l], BF16)
-                n, k = host[name][l].shape
-                assert np.array_equal(step.w8[name][l].numpy(np.uint8, (n, k)), q[name, l][0]), f"{name}[{l}] bytes"
-                assert np.array_equal(step.w8_scale[name][l].numpy(np.float32, (n,)), q[name, l][1]), f"{name}[{l}] scales"
-        x_prev = dl(step.trace[0][2]["out"], (B, H))
-        assert np.array_equal(x_prev, EO.embedding(ids, host["emb"]))
-        for (_, l, t) in step.trace[1:-1]:
-            x, xn1, qkv_pre = dl(t["x"], (B, H)), dl(t["xn1"], (B, H)), dl(t["qkv_pre"], (B, qw))
-            assert np.array_equal(x, x_prev)
-            close_linear(qkv_pre, linear_fp8w(xn1, *q["wqkv", l], BF16), f"layer {l} qkv projection")
-            att, o, x1, xn2 = dl(t["att"], (B, hd)), dl(t["o"], (B, H)), dl(t["x1"], (B, H)), dl(t["xn2"], (B, H))
-            close_linear(o, linear_fp8w(att, *q["wo", l], BF16), f"layer {l} o projection")
-            assert np.array_equal(x1, EO.add(x, o, BF16))
-            gu, act, dn, x2 = dl(t["gu"], (B, 2 * I)), dl(t["act"], (B, I)), dl(t["dn"], (B, H)), dl(t["x2"], (B, H))
-            close_linear(gu, linear_fp8w(xn2, *q["wgu", l], BF16), f"layer {l} gate/up projection")
-            silu_ref = EO.silu_mul(np.ascontiguousarray(gu[:, :I]), np.ascontiguousarray(gu[:, I:]), BF16)
-            print(f"B={B} layer {l}: SiLU.up differs from the oracle in {(act != silu_ref).sum()} of {act.size} outputs")
-            assert np.array_equal(act, silu_ref), f"layer {l} SiLU.up"
-            close_linear(dn, linear_fp8w(act, *q["wdown", l], BF16), f"layer {l} down projection")
-            assert np.array_equal(x2, EO.add(x1, dn, BF16))
-            x_prev = x2
-        assert np.array_equal(runs[0][1], to_f32(runs[0][0], BF16).argmax(1))
-    assert np.array_equal(runs[0][0], runs[1][0]) and np.array_equal(runs[0][1], runs[1][1])
-    assert all(np.array_equal(a, b) for a, b in zip(runs[0][2] + runs[0][3], runs[1][2] + runs[1][3]))
+    """DecodeStep(weight_dtype="fp8") against the restatement, op by op, and fused against unfused (wq_cases.check_decode_step_op_by_op)."""
+    check_decode_step_op_by_op(gpu, B, "fp8", quantize_rows, linear_fp8w, "w8", "w8_scale")
 
 
 def test_decode_step_over_fp8_weights_refuses_more_than_64_rows(gpu):

@@ -9,6 +9,7 @@ Projections: atoma_linear (weight streaming up to 4 rows, hipBLASLt above), or, 
 quantised once at upload and atoma_linear_decode_fp8w[_residual / _silu_mul], or, with weight_dtype="mxfp4" (batch <= 16), MXFP4 weights
 (e2m1 nibbles + e8m0 block scales) and atoma_linear_decode_mxfp4[_residual / _silu_mul].  Everything is enqueued on one stream, so a step can be captured in a hipGraph.
 """
+import collections
 import os
 import sys
 
@@ -32,6 +33,22 @@ class Config:
 LLAMA_3_1_8B = Config(32, 4096, 32, 8, 128, 14336, 128256)
 
 
+# A quantised format of the q/k/v, o, gate/up and down weights, everything DecodeStep needs to know about it: sizes(n, k) -> (weight bytes, scale
+# bytes) of one [n, k] matrix; quantise(w_ptr, n, k, out_ptr, scale_ptr, stream) -> rc enqueues one matrix; strides(k) = the arguments its
+# projection entries take between N and y_row_stride (after x_row_stride); entry + "" / "_residual" / "_silu_mul" name the three entries.
+WeightFormat = collections.namedtuple("WeightFormat", "name label max_batch sizes quantise strides entry")
+WEIGHT_FORMATS = {
+    # e4m3fn bytes [N, K] with one f32 scale per output row [N]
+    "fp8": WeightFormat("fp8", "fp8", 64, lambda n, k: (n * k, n * 4),
+                        lambda w, n, k, q, sc, s: ah.lib.atoma_quantize_weight_fp8(w, n, k, k, BF16, q, k, sc, s),
+                        lambda k: (k,), "atoma_linear_decode_fp8w"),
+    # e2m1 nibbles [N, K / 2] with one e8m0 scale byte per 32 inputs [N, K / 32]
+    "mxfp4": WeightFormat("mxfp4", "MXFP4", 16, lambda n, k: (n * k // 2, n * k // 32),
+                          lambda w, n, k, q, sc, s: ah.lib.atoma_quantize_weight_mxfp4(w, n, k, k, BF16, q, k // 2, sc, k // 32, s),
+                          lambda k: (k // 2, k // 32), "atoma_linear_decode_mxfp4"),
+}
+
+
 class DecodeStep:
     """Device-resident weights, caches and activations of a model + `run()` = one decode step for `batch` sequences."""
 
@@ -47,23 +64,18 @@ class DecodeStep:
         c = self.cfg = cfg
         self.B, self.stream, self.keep = batch, stream, keep_intermediates
         self.allreduce = allreduce
-        # weight_dtype="fp8": the q/k/v, o, gate/up and down weights as e4m3fn bytes with one f32 scale per output row, quantised ONCE here
-        # (atoma_quantize_weight_fp8) and multiplied by atoma_linear_decode_fp8w[_residual / _silu_mul]; lm_head and the embedding stay 16-bit.
-        # The fused-RMSNorm and fused q/k/v + RoPE + cache forms do not exist over fp8 weights: the norms and atoma_rope_qk_cache run on their own.
-        # weight_dtype="mxfp4": the same four weights as e2m1 nibbles [N, K / 2] with one e8m0 scale byte per 32 inputs [N, K / 32]
-        # (atoma_quantize_weight_mxfp4, atoma_linear_decode_mxfp4[_residual / _silu_mul]), at most 16 rows; everything else as for fp8.
+        # weight_dtype="fp8" / "mxfp4" (WEIGHT_FORMATS): the q/k/v, o, gate/up and down weights quantised ONCE here and multiplied by the format's
+        # atoma_linear_decode_<format>[_residual / _silu_mul]; lm_head and the embedding stay 16-bit.  The fused-RMSNorm and fused q/k/v + RoPE +
+        # cache forms do not exist over quantised weights: the norms and atoma_rope_qk_cache run on their own.
         if weight_dtype not in ("bf16", "fp8", "mxfp4"):
             raise ValueError(f"DecodeStep: weight_dtype must be 'bf16', 'fp8' or 'mxfp4', not {weight_dtype!r}")
+        f = self.wq = WEIGHT_FORMATS.get(weight_dtype)     # None: 16-bit weights
         self.fp8w = weight_dtype == "fp8"
         self.mxfp4 = weight_dtype == "mxfp4"
-        if self.fp8w and batch > 64:
-            raise ValueError(f"DecodeStep(weight_dtype='fp8'): batch {batch} > 64 -- the fp8-weight projections serve at most 64 rows")
-        if self.fp8w and allreduce is not None:
-            raise ValueError("DecodeStep(weight_dtype='fp8'): tensor-parallel ranks are not supported with fp8 weights")
-        if self.mxfp4 and batch > 16:
-            raise ValueError(f"DecodeStep(weight_dtype='mxfp4'): batch {batch} > 16 -- the MXFP4-weight projections serve at most 16 rows")
-        if self.mxfp4 and allreduce is not None:
-            raise ValueError("DecodeStep(weight_dtype='mxfp4'): tensor-parallel ranks are not supported with MXFP4 weights")
+        if f and batch > f.max_batch:
+            raise ValueError(f"DecodeStep(weight_dtype='{f.name}'): batch {batch} > {f.max_batch} -- the {f.label}-weight projections serve at most {f.max_batch} rows")
+        if f and allreduce is not None:
+            raise ValueError(f"DecodeStep(weight_dtype='{f.name}'): tensor-parallel ranks are not supported with {f.label} weights")
         # allreduce_norm(in, residual, weight, x_out, norm_out, rows) -> True when it enqueued "x_out = residual + allreduce(in); norm_out =
         # RMSNorm(x_out) * weight" as ONE launch (atoma_xgmi_allreduce_add_rms_norm / atoma_allreduce_add_rms_norm); False = not available now:
         # the step falls back to allreduce + atoma_add_rms_norm (same bits)
@@ -87,14 +99,12 @@ class DecodeStep:
         self.norm_in_proj = os.environ.get("ATOMA_STEP_NORM_IN_PROJ", "1") != "0"   # fused path: RMSNorm inside the q/k/v and gate/up projections (A/B switch)
         self.fuse_norm = fuse_norm and not keep_intermediates and not self.fused   # residual add + the RMSNorm that follows it in one kernel
         self.w = weights                                   # dict of DeviceBuffers, see random_weights / upload_weights
-        self.w8, self.w8_scale = {}, {}                    # fp8w: name -> per-layer DeviceBuffers (bytes [N, K]; f32 [N])
-        self.w4, self.w4_scale = {}, {}                    # mxfp4: name -> per-layer DeviceBuffers (nibble bytes [N, K / 2]; e8m0 bytes [N, K / 32])
-        if self.fp8w:
-            self._quantise(weights, self.w8, self.w8_scale, lambda n, k: (n * k, n * 4),
-                           lambda w, n, k, q, sc: ah.lib.atoma_quantize_weight_fp8(w, n, k, k, BF16, q, k, sc, stream.s))
-        if self.mxfp4:
-            self._quantise(weights, self.w4, self.w4_scale, lambda n, k: (n * k // 2, n * k // 32),
-                           lambda w, n, k, q, sc: ah.lib.atoma_quantize_weight_mxfp4(w, n, k, k, BF16, q, k // 2, sc, k // 32, stream.s))
+        self.wq_w, self.wq_scale = {}, {}                  # quantised weights: name -> per-layer DeviceBuffers (sizes: WeightFormat.sizes)
+        # the same buffers under the names of their format: fp8 bytes [N, K] + f32 [N]; nibble bytes [N, K / 2] + e8m0 bytes [N, K / 32]
+        self.w8, self.w8_scale = (self.wq_w, self.wq_scale) if self.fp8w else ({}, {})
+        self.w4, self.w4_scale = (self.wq_w, self.wq_scale) if self.mxfp4 else ({}, {})
+        if f:
+            self._quantise(weights)
         page_elems = c.page * c.hk * c.d
         # kv_fp8: the KV cache holds e4m3fn bytes with one dequantisation scale per kv head (atoma_rope_qk_cache_fp8 /
         # atoma_paged_decode_fp8); everything else of the step is unchanged
@@ -133,20 +143,21 @@ class DecodeStep:
             greedy["temperature"], greedy["top_p"], greedy["repetition_penalty"] = 1.0, 1.0, 1.0
             self.params.upload(greedy)
 
-    def _quantise(self, weights, out, out_scale, sizes, quantise):
-        """The q/k/v, o, gate/up and down weights quantised once, at upload: sizes(n, k) -> (weight bytes, scale bytes) of one matrix,
-        quantise(w_ptr, n, k, out_ptr, scale_ptr) -> rc enqueues one matrix.  The fused-norm and fused q/k/v forms exist for 16-bit weights only."""
-        c = self.cfg
+    def _quantise(self, weights):
+        """The q/k/v, o, gate/up and down weights quantised once, at upload, in the step's WeightFormat.  The fused-norm and fused q/k/v forms
+        exist for 16-bit weights only."""
+        c, f = self.cfg, self.wq
         self.qkv_fused = self.norm_in_proj = False
+        self.q_linear, self.q_residual, self.q_silu_mul = (getattr(ah.lib, f.entry + suffix) for suffix in ("", "_residual", "_silu_mul"))
         shapes = dict(wqkv=(c.qkv, c.hidden), wo=(c.hidden, c.h * c.d), wgu=(2 * c.inter, c.hidden), wdown=(c.hidden, c.inter))
         for name, (n, k) in shapes.items():
-            out[name], out_scale[name] = [], []
+            self.wq_w[name], self.wq_scale[name] = [], []
             for l in range(c.layers):
-                nbytes, sbytes = sizes(n, k)
+                nbytes, sbytes = f.sizes(n, k)
                 q, sc = ah.DeviceBuffer(nbytes), ah.DeviceBuffer(sbytes)
-                self._ok(quantise(weights[name][l].ptr, n, k, q.ptr, sc.ptr), f"quantising {name}[{l}]")
-                out[name].append(q)
-                out_scale[name].append(sc)
+                self._ok(f.quantise(weights[name][l].ptr, n, k, q.ptr, sc.ptr, self.stream.s), f"quantising {name}[{l}]")
+                self.wq_w[name].append(q)
+                self.wq_scale[name].append(sc)
         self.stream.synchronize()
 
     def _buf(self, name, layer, nbytes):
@@ -201,12 +212,10 @@ class DecodeStep:
             raise RuntimeError(f"{what}: {ah.last_error()}")
 
     def _proj(self, name, l, x, y, K, N, what):
-        """y [B, N] = x [B, K] . w[name][l]^T through the step's projection entry (fp8 or 16-bit weights)."""
+        """y [B, N] = x [B, K] . w[name][l]^T through the step's projection entry (quantised or 16-bit weights)."""
         B, s = self.B, self.stream.s
-        if self.fp8w:
-            self._ok(ah.lib.atoma_linear_decode_fp8w(x.ptr, self.w8[name][l].ptr, self.w8_scale[name][l].ptr, y.ptr, B, K, N, K, K, N, BF16, s), what)
-        elif self.mxfp4:
-            self._ok(ah.lib.atoma_linear_decode_mxfp4(x.ptr, self.w4[name][l].ptr, self.w4_scale[name][l].ptr, y.ptr, B, K, N, K, K // 2, K // 32, N, BF16, s), what)
+        if self.wq:
+            self._ok(self.q_linear(x.ptr, self.wq_w[name][l].ptr, self.wq_scale[name][l].ptr, y.ptr, B, K, N, K, *self.wq.strides(K), N, BF16, s), what)
         else:
             self._ok(self.linear(x.ptr, self.w[name][l].ptr, y.ptr, B, K, N, K, K, N, BF16, s), what)
 
@@ -266,18 +275,12 @@ class DecodeStep:
             # ping-pong the residual stream so that no kernel reads and writes the same buffer
             x2 = self._buf("x2", l, B * H * 2) if self.keep else self._buf("x2a" if l % 2 == 0 else "x2b", 0, B * H * 2)
             o = gu = dn = None
-            if self.fused and self.fp8w:
-                w8, sc = self.w8, self.w8_scale
-                self._ok(L.atoma_linear_decode_fp8w_residual(att.ptr, w8["wo"][l].ptr, sc["wo"][l].ptr, x.ptr, x1.ptr, B, hd, H, hd, hd, H, H, BF16, s), "o projection + residual")
+            if self.fused and self.wq:
+                qw, sc, st = self.wq_w, self.wq_scale, self.wq.strides
+                self._ok(self.q_residual(att.ptr, qw["wo"][l].ptr, sc["wo"][l].ptr, x.ptr, x1.ptr, B, hd, H, hd, *st(hd), H, H, BF16, s), "o projection + residual")
                 self._ok(L.atoma_rms_norm(x1.ptr, self.w["norm2"][l].ptr, xn2.ptr, B, H, H, H, c.eps, BF16, s), "rms_norm")
-                self._ok(L.atoma_linear_decode_fp8w_silu_mul(xn2.ptr, w8["wgu"][l].ptr, sc["wgu"][l].ptr, act.ptr, B, H, c.inter, H, H, c.inter, BF16, s), "gate/up projection + silu * up")
-                self._ok(L.atoma_linear_decode_fp8w_residual(act.ptr, w8["wdown"][l].ptr, sc["wdown"][l].ptr, x1.ptr, x2.ptr, B, c.inter, H, c.inter, c.inter, H, H, BF16, s), "down projection + residual")
-            elif self.fused and self.mxfp4:
-                w4, sc = self.w4, self.w4_scale
-                self._ok(L.atoma_linear_decode_mxfp4_residual(att.ptr, w4["wo"][l].ptr, sc["wo"][l].ptr, x.ptr, x1.ptr, B, hd, H, hd, hd // 2, hd // 32, H, H, BF16, s), "o projection + residual")
-                self._ok(L.atoma_rms_norm(x1.ptr, self.w["norm2"][l].ptr, xn2.ptr, B, H, H, H, c.eps, BF16, s), "rms_norm")
-                self._ok(L.atoma_linear_decode_mxfp4_silu_mul(xn2.ptr, w4["wgu"][l].ptr, sc["wgu"][l].ptr, act.ptr, B, H, c.inter, H, H // 2, H // 32, c.inter, BF16, s), "gate/up projection + silu * up")
-                self._ok(L.atoma_linear_decode_mxfp4_residual(act.ptr, w4["wdown"][l].ptr, sc["wdown"][l].ptr, x1.ptr, x2.ptr, B, c.inter, H, c.inter, c.inter // 2, c.inter // 32, H, H, BF16, s), "down projection + residual")
+                self._ok(self.q_silu_mul(xn2.ptr, qw["wgu"][l].ptr, sc["wgu"][l].ptr, act.ptr, B, H, c.inter, H, *st(H), c.inter, BF16, s), "gate/up projection + silu * up")
+                self._ok(self.q_residual(act.ptr, qw["wdown"][l].ptr, sc["wdown"][l].ptr, x1.ptr, x2.ptr, B, c.inter, H, c.inter, *st(c.inter), H, H, BF16, s), "down projection + residual")
             elif self.fused:
                 self._ok(L.atoma_linear_decode_residual(att.ptr, self.w["wo"][l].ptr, x.ptr, x1.ptr, B, hd, H, hd, hd, H, H, BF16, s), "o projection + residual")
                 if self.norm_in_proj:
